@@ -1,5 +1,8 @@
 import os
+import pathlib
+import shutil
 import sys
+import tempfile
 
 import pytest
 
@@ -33,3 +36,27 @@ def nat():
 def reference_crd_path():
     p = "/root/reference/charts/bacchus-gpu-controller/templates/crd.yaml"
     return p if os.path.exists(p) else None
+
+
+# sun_path of an AF_UNIX address holds 107 bytes; the longest name a test puts under its
+# tmp_path is "pod-resources/kubelet.sock"
+_UNIX_PATH_MAX = 107
+_LONGEST_SOCKET_SUFFIX = len("/pod-resources/kubelet.sock")
+
+
+@pytest.fixture
+def tmp_path(tmp_path):
+    """pytest's tmp_path, unless it lies so deep (a long TMPDIR or home directory) that the
+    Unix sockets the tests bind under it would not fit in a socket address: then a short
+    directory of its own, removed after the test."""
+    if len(os.fsencode(str(tmp_path))) + _LONGEST_SOCKET_SUFFIX <= _UNIX_PATH_MAX:
+        yield tmp_path
+        return
+    roots = [r for r in ("/tmp", "/var/tmp", "/dev/shm") if os.path.isdir(r) and os.access(r, os.W_OK | os.X_OK)]
+    if not roots:
+        pytest.fail(f"{tmp_path} is too long for a Unix socket path and no short temporary directory is writable")
+    short = tempfile.mkdtemp(prefix="bgc-", dir=roots[0])
+    try:
+        yield pathlib.Path(short)
+    finally:
+        shutil.rmtree(short, ignore_errors=True)

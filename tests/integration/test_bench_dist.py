@@ -14,17 +14,25 @@ from bacchus_gpu_controller_amd.testing.cluster import free_port
 pytestmark = pytest.mark.slow
 
 
-def test_bench_two_ranks_gloo():
+def test_bench_two_ranks_gloo(tmp_path):
+    import numpy as np
+
     env = dict(os.environ, BGC_BENCH_CPU="1", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(REPO_ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "20", "--rounds", "2",
-           "--latency-rates", "200", "--latency-window-s", "1", "--no-reference-arms"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "20", "--rounds", "2", "--full",
+           "--latency-rates", "200", "--latency-window-s", "1", "--no-reference-arms",
+           "--dump-outputs", str(tmp_path / "dump")]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=REPO_ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout  # only rank 0 prints
     d = json.loads(lines[0])
+    # --dump-outputs: both ranks' last timed step (2 rounds of 20 tenants each), in rank order
+    assert np.load(tmp_path / "dump" / "round_counts.npy").tolist() == [[20, 0, 0]] * 4
+    assert (np.load(tmp_path / "dump" / "tenant_children.npy") == np.ones((40, 3), dtype=np.float32)).all()
+    quota = np.load(tmp_path / "dump" / "tenant_quota.npy")
+    assert quota.shape == (40, 7) and (quota[:, 4] == 1).all()  # requests.amd.com/gpu of every tenant
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1
     # a step is `rounds` rounds of `batch` tenants per rank
     assert d["config"]["global_batch"] == 2 * 20 * 2 and d["config"]["parallelism"] == "dp2"
@@ -79,11 +87,11 @@ def test_bench_approve_after_create():
 
 
 def test_default_run_carries_the_reference_arms():
-    """The default single-GPU run also times the reference's controller behaviour on the same
+    """The default single-GPU run with --full also times the reference's controller behaviour on the same
     stack and both controllers at an etcd-like write latency; every
     arm's percentiles come from whole windows."""
     cmd = [sys.executable, os.path.join(REPO_ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "20",
-           "--rounds", "1", "--no-tuned-phase", "--no-http1-phase", "--arm-steps", "2", "--arm-warmup", "1",
+           "--rounds", "1", "--full", "--no-tuned-phase", "--no-http1-phase", "--arm-steps", "2", "--arm-warmup", "1",
            "--latency-rates", "100,200", "--latency-window-s", "1", "--time-budget-s", "0"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO_ROOT,
                        env=dict(os.environ, BGC_BENCH_CPU="1"))
@@ -129,6 +137,46 @@ def test_default_run_carries_the_reference_arms():
     assert pi["cpus"]["fixtures"] and pi["cpus"]["product"]
 
 
+def _plain_run(dump):
+    cmd = [sys.executable, os.path.join(REPO_ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--batch", "20", "--rounds", "2", "--dump-outputs", dump]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO_ROOT,
+                       env=dict(os.environ, BGC_BENCH_CPU="1"))
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout  # the result line and nothing else
+    return json.loads(lines[0])
+
+
+def test_plain_run_times_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full only the headline phase runs; --dump-outputs writes what its last timed
+    step produced, the same from run to run."""
+    import numpy as np
+
+    d = _plain_run(str(tmp_path / "a"))
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ready_crs"] == 2 * 2 * 20 and d["failed_crs"] == 0
+    assert d["value"] > 0 and d["unit"] == "CR/s" and d["higher_is_better"] is True and d["dtype"] == "none"
+    # the milliseconds one timed step took: ready_crs / value is the timed region
+    assert d["ms_per_step"] == pytest.approx(d["ready_crs"] / d["value"] / 2 * 1e3, rel=1e-3)
+    # ... which lies inside the phase's wall time (that one includes the warmup step), and each
+    # step's two rounds of 20 tenants through the whole stack take longer than a millisecond
+    assert 1.0 < d["ms_per_step"] and 2 * d["ms_per_step"] < d["phase_wall_s"]["m"] * 1e3
+    assert set(d["phase_wall_s"]) == {"setup", "m", "total"}
+    for k in ("product_isolated", "tuned", "webhook_http1", "reference_controller", "write_latency_2ms",
+              "latency_at_rate", "stage_table", "rccl_xgmi", "skipped_phases"):
+        assert k not in d, k
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("round_counts", "tenant_children", "tenant_quota")}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(f"{n}.npy" for n in a)
+    assert a["round_counts"].dtype == np.float64 and a["round_counts"].tolist() == [[20, 0, 0]] * 2
+    assert a["tenant_children"].dtype == np.float32 and (a["tenant_children"] == np.ones((20, 3))).all()
+    # the sheet's row of every tenant: 1 GPU, 8 vCPU, 64 GiB memory, 100 GiB storage, no partition
+    row = [8, 64 * 2.0 ** 30, 8, 64 * 2.0 ** 30, 1, 100 * 2.0 ** 30, 0]
+    assert a["tenant_quota"].dtype == np.float64 and a["tenant_quota"].tolist() == [row] * 20
+    _plain_run(str(tmp_path / "b"))
+    for n, v in a.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{n}.npy")), n
+
+
 def test_auto_concurrency_follows_cpu_share():
     from bacchus_gpu_controller_amd.bench.harness import auto_concurrency, effective_cpus
 
@@ -159,7 +207,7 @@ def test_time_budget_skips_the_secondary_phases():
     budget, the secondary phases (write-latency arms, tuned, HTTP/1.1 webhook) are left out
     and listed; the headline, the reference controller and latency_at_rate always run."""
     cmd = [sys.executable, os.path.join(REPO_ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "20",
-           "--rounds", "1", "--latency-rates", "100", "--latency-window-s", "1", "--no-isolated-phase",
+           "--rounds", "1", "--full", "--latency-rates", "100", "--latency-window-s", "1", "--no-isolated-phase",
            "--time-budget-s", "0.5"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO_ROOT,
                        env=dict(os.environ, BGC_BENCH_CPU="1"))

@@ -164,7 +164,8 @@ def test_workqueue_shard_timer_and_shutdown(nat):
     ("warn,controller=debug", "debug", "controller", True),
     ("warn,controller=debug", "info", "admission", False),
     ("controller=trace", "info", "admission", False),     # no default => off for others
-    ("kube=debug,info", "debug", "kube::watcher", True),  # module-path prefix
+    # module-path prefix (the id is spelled out: "::" inside a test id reads as a node separator)
+    pytest.param("kube=debug,info", "debug", "kube::watcher", True, id="kube=debug,info-debug-kube.watcher-True"),
     ("", "info", "x", True),                              # empty => INFO default
 ])
 def test_rust_log_targets(nat, spec, level, target, on):

@@ -341,7 +341,15 @@ def test_every_node_agent_config_key_reaches_the_binary():
     assert env["CONF_DIAG_SOAK_LAUNCHES"] == "0"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CHART), reason="reference chart not available")
+def reference_release(release, values):
+    """What the reference chart renders to for one release: the (kind, name) of every object
+    and each Deployment's spec.selector, recorded in tests/golden/."""
+    with open(os.path.join(REPO_ROOT, "tests", "golden", "reference_release_objects.json")) as f:
+        case = next(c for c in json.load(f)
+                    if c["release"] == release and c["values"] == values and c["namespace"] == NS)
+    return {tuple(o) for o in case["objects"]}, case["deployment_selectors"]
+
+
 @pytest.mark.parametrize("release", ["bgc", "bacchus-gpu-prod"])
 @pytest.mark.parametrize("values", [{}, {"fullnameOverride": "gpuctl"}, {"nameOverride": "tenancy"},
                                     {"nameOverride": "tenancy", "fullnameOverride": "gpuctl"}])
@@ -350,15 +358,16 @@ def test_in_place_upgrade_from_a_reference_release(release, values):
     reference renders keeps its name (nothing orphaned), and every Deployment keeps the
     reference's spec.selector (immutable: a different one fails `helm upgrade`)."""
     rel = {"Name": release, "Namespace": NS}
-    ref = manifests(render_chart(REF_CHART, values, rel))
+    ref_names, ref_selectors = reference_release(release, values)
     ours = manifests(render_chart(CHART, values, rel))
     names = lambda objs: {(o["kind"], o["metadata"]["name"]) for o in objs}
-    assert names(ref) <= names(ours), names(ref) - names(ours)
-    ref_dep, our_dep = by_kind(ref, "Deployment"), by_kind(ours, "Deployment")
-    for name, d in ref_dep.items():
-        assert our_dep[name]["spec"]["selector"] == d["spec"]["selector"], name
+    assert ref_names and ref_names <= names(ours), ref_names - names(ours)
+    our_dep = by_kind(ours, "Deployment")
+    assert len(ref_selectors) == 3
+    for name, selector in ref_selectors.items():
+        assert our_dep[name]["spec"]["selector"] == selector, name
         labels = our_dep[name]["spec"]["template"]["metadata"]["labels"]
-        assert d["spec"]["selector"]["matchLabels"].items() <= labels.items()
+        assert selector["matchLabels"].items() <= labels.items()
     # the Q1 fix lives in the (mutable) Service selector and the pod labels only
     svc = next(iter(by_kind(ours, "Service").values()))
     assert svc["spec"]["selector"]["app.kubernetes.io/component"] == "admission"

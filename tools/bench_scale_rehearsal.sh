@@ -8,12 +8,12 @@
 set -o pipefail
 out=${OUT:-gpurun_out/scale}
 mkdir -p $out
-timeout -k 10 240 python -u bench.py --steps 30 --warmup 3 --report-cpu --no-tuned-phase $EXTRA \
+timeout -k 10 240 python -u bench.py --steps 30 --warmup 3 --full --report-cpu --no-tuned-phase $EXTRA \
   --json-out $out/n1.json > $out/n1.log 2>&1 || exit 1
 for n in 2 4 8; do
   BGC_BENCH_CPU=1 timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
     --master-addr 127.0.0.1 --master-port $((29600+n)) bench.py --gpus $n --steps 20 --warmup 3 \
-    --report-cpu --no-tuned-phase $EXTRA --json-out $out/cpu_n$n.json > $out/cpu_n$n.log 2>&1 || exit 1
+    --full --report-cpu --no-tuned-phase $EXTRA --json-out $out/cpu_n$n.json > $out/cpu_n$n.log 2>&1 || exit 1
 done
 python3 - "$out" <<'PY'
 import json, sys

@@ -50,9 +50,9 @@ run_arm() {  # name, rep, spec
   if [ "$nproc" -gt 1 ]; then
     env "${envs[@]}" BGC_BENCH_CPU=1 timeout -k 10 "$limit" python -u -m torch.distributed.run --nnodes=1 \
       --nproc-per-node "$nproc" --master-addr 127.0.0.1 --master-port $((29600 + nproc)) bench.py --gpus "$nproc" \
-      --steps 20 --warmup 3 --report-cpu "${args[@]}" --json-out "$out/${name}_$rep.json" > "$out/${name}_$rep.log" 2>&1
+      --steps 20 --warmup 3 --full --report-cpu "${args[@]}" --json-out "$out/${name}_$rep.json" > "$out/${name}_$rep.log" 2>&1
   else
-    env "${envs[@]}" timeout -k 10 "$limit" python -u bench.py --report-cpu "${args[@]}" \
+    env "${envs[@]}" timeout -k 10 "$limit" python -u bench.py --full --report-cpu "${args[@]}" \
       --json-out "$out/${name}_$rep.json" > "$out/${name}_$rep.log" 2>&1
   fi
 }

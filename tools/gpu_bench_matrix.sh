@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # Headline bench matrix on a 1-GPU MI355X box (run through gpurun from the repo root).
-#   1. default bench.py (BASELINE config #3: 100 in flight, RUST_LOG=info, tuned phase)
+#   1. default bench.py --full (BASELINE config #3: 100 in flight, RUST_LOG=info, tuned phase)
 #   2. this build vs the reference's controller behaviour, at 0 and 2 ms API write latency
 #   3. full reference semantics (60 s sheet tick) at 0 ms, few steps
 #   4. create -> approve -> Ready at the product's 5 s sheet poll
@@ -14,7 +14,7 @@ run() {  # name, timeout, bench args...
   local name=$1 t=$2
   shift 2
   echo "[$(date +%T)] $name: bench.py $*"
-  timeout -k 10 "$t" python -u bench.py "$@" --json-out "$OUT/$name.json" > "$OUT/$name.log" 2>&1
+  timeout -k 10 "$t" python -u bench.py --full "$@" --json-out "$OUT/$name.json" > "$OUT/$name.log" 2>&1
 }
 run default 300 &&
 run this_wl0 300 --no-tuned-phase &&

@@ -10,6 +10,6 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 for i in $(seq 1 "$RUNS"); do
   s=$(date +%s)
-  timeout -k 10 420 python -u bench.py --report-cpu > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err" || exit $?
+  timeout -k 10 420 python -u bench.py --full --report-cpu > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err" || exit $?
   echo "bench_$i run_s=$(( $(date +%s) - s ))" | tee -a "$OUT/timing.txt"
 done

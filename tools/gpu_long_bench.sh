@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 # the headline phase only: the secondary phases and reference arms would run as long
 timeout -k 10 600 python -u bench.py --steps "$STEPS" --warmup 5 --no-tuned-phase --no-http1-phase --no-reference-arms \
     > "$OUT/bench_long.json" 2> "$OUT/bench_long.err" &&
-timeout -k 10 300 python -u bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+timeout -k 10 300 python -u bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 rc=$?
 cut -c1-400 "$OUT/bench_long.json" "$OUT/bench_default.json"
 exit $rc

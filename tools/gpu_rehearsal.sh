@@ -13,7 +13,7 @@ bench_runs() {
   for i in $(seq 1 "$RUNS"); do
     s=$(date +%s)
     # shellcheck disable=SC2086
-    timeout -k 10 420 python -u bench.py ${BENCH_ARGS:-} > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err" || return $?
+    timeout -k 10 420 python -u bench.py --full ${BENCH_ARGS:-} > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err" || return $?
     echo "bench_$i run_s=$(( $(date +%s) - s ))" >> "$OUT/timing.txt"
   done
 }

@@ -11,7 +11,7 @@ poll's split into on-CPU time, run-queue wait and blocked time (core/schedstat.h
   quiet:  kube-lite + the node agent alone, 1 GPU, polling every 250 ms (the bench's
           cadence) for --seconds
   bench:  bench.py with its node agent wrapped the same way (arguments after "--" go to
-          bench.py)
+          bench.py, e.g. --full to poll through the secondary phases too)
 
 Writes <out>/<mode>/summary.json: per roctx range n, mean, p50, p99, max (us), and the
 poll split percentiles.

@@ -7,7 +7,7 @@ out=${1:?out dir}; shift
 mkdir -p "$out/raw"
 out=$(cd "$out" && pwd)
 rm -f "$out"/raw/*.prof
-BGC_CPU_PROFILE="$out/raw/%p.prof" python3 bench.py --report-cpu --json-out "$out/bench.json" "$@" > "$out/bench.log" 2>&1
+BGC_CPU_PROFILE="$out/raw/%p.prof" python3 bench.py --full --report-cpu --json-out "$out/bench.json" "$@" > "$out/bench.log" 2>&1
 for f in "$out"/raw/*.prof; do
   bin=$(grep -m1 -o "/bin/[a-z-]*$" "$f" | head -1 | sed 's#/bin/##')
   [ -n "$bin" ] || bin=unknown

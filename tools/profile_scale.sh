@@ -9,7 +9,7 @@ out=$(cd "$out" && pwd)
 rm -f "$out"/raw/*.prof
 BGC_CPU_PROFILE="$out/raw/%p.prof" BGC_BENCH_CPU=1 timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 \
   --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $((29700 + n)) bench.py --gpus "$n" --steps 20 --warmup 3 \
-  --report-cpu --no-tuned-phase --json-out "$out/bench.json" > "$out/bench.log" 2>&1
+  --full --report-cpu --no-tuned-phase --json-out "$out/bench.json" > "$out/bench.log" 2>&1
 for f in "$out"/raw/*.prof; do
   bin=$(grep -m1 -o "/bin/[a-z-]*$" "$f" | head -1 | sed 's#/bin/##')
   [ -n "$bin" ] || bin=unknown
