@@ -1,4 +1,4 @@
-"""HIP/CDNA4 GPU health kernels (native/gpu/hip/gpu_diag.hip) exposed to Python.
+"""HIP/CDNA4 GPU health kernels (native/gpu/hip/: hbm.hip, mfma.hip, gemm_soak.hip) exposed to Python.
 
 These are the only compute kernels in the framework: the reference controller has none
 (SURVEY §2.5).  They back the node agent's diagnostics before a GPU is advertised

@@ -40,25 +40,25 @@ std::string so_dir() {
 Diag::Diag(const std::string& path) : path_(path) {
   lib_ = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
   if (!lib_) throw std::runtime_error("cannot load " + path + ": " + dlerror());
-  device_count_ = reinterpret_cast<int (*)()>(dlsym(lib_, "bgc_diag_device_count"));
-  hbm_ = reinterpret_cast<int (*)(int, uint64_t, int, uint32_t, bgc_hbm_result*)>(dlsym(lib_, "bgc_diag_hbm"));
-  mfma_ = reinterpret_cast<int (*)(int, int, int, uint32_t, bgc_mfma_result*)>(dlsym(lib_, "bgc_diag_mfma"));
-  lowp_ = reinterpret_cast<int (*)(int, int, int, uint32_t, bgc_lowp_result*)>(dlsym(lib_, "bgc_diag_mfma_lowp"));
-  arch_ = reinterpret_cast<int (*)(int, char*, size_t)>(dlsym(lib_, "bgc_diag_device_arch"));
-  gemm_ = reinterpret_cast<int (*)(int, int, int, int, const uint16_t*, const uint16_t*, float*)>(
-      dlsym(lib_, "bgc_diag_gemm"));
-  burn_ = reinterpret_cast<int (*)(int, int, int, uint32_t, int, bgc_burn_result*)>(dlsym(lib_, "bgc_diag_burn_dtype"));
-  pcie_ = reinterpret_cast<int (*)(int, uint64_t, int, uint32_t, bgc_pcie_result*)>(dlsym(lib_, "bgc_diag_pcie"));
-  soak_ = reinterpret_cast<int (*)(int, int, int, int, int, uint32_t, bgc_soak_result*)>(dlsym(lib_, "bgc_diag_gemm_soak"));
-  tiled_ = reinterpret_cast<int (*)(int, int, int, int, const uint16_t*, const uint16_t*, float*)>(
-      dlsym(lib_, "bgc_diag_gemm_tiled"));
-  mx_gemm_ = reinterpret_cast<int (*)(int, int, int, int, int, const uint8_t*, const uint8_t*, const uint8_t*,
-                                      const uint8_t*, float*)>(dlsym(lib_, "bgc_diag_mx_gemm"));
-  walk_ = reinterpret_cast<int (*)(int, double, uint64_t, int, uint32_t, bgc_hbm_walk_result*)>(
-      dlsym(lib_, "bgc_diag_hbm_walk"));
-  bdf_ = reinterpret_cast<int (*)(int, char*, size_t)>(dlsym(lib_, "bgc_diag_device_bdf"));
-  last_error_ = reinterpret_cast<const char* (*)()>(dlsym(lib_, "bgc_diag_last_error"));
-  auto abi = reinterpret_cast<int (*)()>(dlsym(lib_, "bgc_diag_abi_version"));
+  // each symbol is loaded as the type gpu_diag.h declares it with
+#define BGC_DIAG_SYM(member, name) member = reinterpret_cast<decltype(&name)>(dlsym(lib_, #name))
+  BGC_DIAG_SYM(device_count_, bgc_diag_device_count);
+  BGC_DIAG_SYM(hbm_, bgc_diag_hbm);
+  BGC_DIAG_SYM(mfma_, bgc_diag_mfma);
+  BGC_DIAG_SYM(lowp_, bgc_diag_mfma_lowp);
+  BGC_DIAG_SYM(arch_, bgc_diag_device_arch);
+  BGC_DIAG_SYM(gemm_, bgc_diag_gemm);
+  BGC_DIAG_SYM(burn_, bgc_diag_burn_dtype);
+  BGC_DIAG_SYM(pcie_, bgc_diag_pcie);
+  BGC_DIAG_SYM(soak_, bgc_diag_gemm_soak);
+  BGC_DIAG_SYM(tiled_, bgc_diag_gemm_tiled);
+  BGC_DIAG_SYM(mx_gemm_, bgc_diag_mx_gemm);
+  BGC_DIAG_SYM(walk_, bgc_diag_hbm_walk);
+  BGC_DIAG_SYM(bdf_, bgc_diag_device_bdf);
+  BGC_DIAG_SYM(last_error_, bgc_diag_last_error);
+  decltype(&bgc_diag_abi_version) abi = nullptr;
+  BGC_DIAG_SYM(abi, bgc_diag_abi_version);
+#undef BGC_DIAG_SYM
   if (!device_count_ || !hbm_ || !mfma_ || !lowp_ || !arch_ || !gemm_ || !burn_ || !pcie_ || !soak_ || !tiled_ ||
       !mx_gemm_ || !walk_ || !bdf_ || !last_error_ || !abi ||
       abi() != BGC_DIAG_ABI_VERSION) {

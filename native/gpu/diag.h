@@ -97,21 +97,20 @@ class Diag {
   explicit Diag(const std::string& path);
   std::string path_;
   void* lib_ = nullptr;
-  int (*device_count_)() = nullptr;
-  int (*hbm_)(int, uint64_t, int, uint32_t, bgc_hbm_result*) = nullptr;
-  int (*mfma_)(int, int, int, uint32_t, bgc_mfma_result*) = nullptr;
-  int (*lowp_)(int, int, int, uint32_t, bgc_lowp_result*) = nullptr;
-  int (*arch_)(int, char*, size_t) = nullptr;
-  int (*gemm_)(int, int, int, int, const uint16_t*, const uint16_t*, float*) = nullptr;
-  int (*burn_)(int, int, int, uint32_t, int, bgc_burn_result*) = nullptr;
-  int (*pcie_)(int, uint64_t, int, uint32_t, bgc_pcie_result*) = nullptr;
-  int (*soak_)(int, int, int, int, int, uint32_t, bgc_soak_result*) = nullptr;
-  int (*tiled_)(int, int, int, int, const uint16_t*, const uint16_t*, float*) = nullptr;
-  int (*mx_gemm_)(int, int, int, int, int, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*,
-                  float*) = nullptr;
-  int (*walk_)(int, double, uint64_t, int, uint32_t, bgc_hbm_walk_result*) = nullptr;
-  int (*bdf_)(int, char*, size_t) = nullptr;
-  const char* (*last_error_)() = nullptr;
+  decltype(&bgc_diag_device_count) device_count_ = nullptr;
+  decltype(&bgc_diag_hbm) hbm_ = nullptr;
+  decltype(&bgc_diag_mfma) mfma_ = nullptr;
+  decltype(&bgc_diag_mfma_lowp) lowp_ = nullptr;
+  decltype(&bgc_diag_device_arch) arch_ = nullptr;
+  decltype(&bgc_diag_gemm) gemm_ = nullptr;
+  decltype(&bgc_diag_burn_dtype) burn_ = nullptr;
+  decltype(&bgc_diag_pcie) pcie_ = nullptr;
+  decltype(&bgc_diag_gemm_soak) soak_ = nullptr;
+  decltype(&bgc_diag_gemm_tiled) tiled_ = nullptr;
+  decltype(&bgc_diag_mx_gemm) mx_gemm_ = nullptr;
+  decltype(&bgc_diag_hbm_walk) walk_ = nullptr;
+  decltype(&bgc_diag_device_bdf) bdf_ = nullptr;
+  decltype(&bgc_diag_last_error) last_error_ = nullptr;
 };
 
 }  // namespace bgc::gpu

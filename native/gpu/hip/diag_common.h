@@ -1,0 +1,120 @@
+// Shared by the diagnostics' sources (gpu_diag.hip, hbm.hip, mfma.hip, gemm_soak.hip): vector
+// types, the hash, the last-error string and the host helpers every entry point uses.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "gpu_diag.h"
+
+namespace bgc_diag __attribute__((visibility("hidden"))) {
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+
+constexpr int kBlock = 256;
+
+extern thread_local std::string g_last_error;  // gpu_diag.hip; read by bgc_diag_last_error()
+
+__host__ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352dU;
+  x ^= x >> 15;
+  x *= 0x846ca68bU;
+  x ^= x >> 16;
+  return x;
+}
+
+#define HIP_TRY(expr)                                                                   \
+  do {                                                                                  \
+    hipError_t _e = (expr);                                                             \
+    if (_e != hipSuccess) {                                                             \
+      bgc_diag::g_last_error = std::string(#expr) + ": " + hipGetErrorString(_e);       \
+      return 1;                                                                         \
+    }                                                                                   \
+  } while (0)
+
+inline int cu_count(int device) {
+  int n = 0;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n <= 0) n = 256;
+  return n;
+}
+
+struct DeviceBuffer {
+  void* p = nullptr;
+  DeviceBuffer() = default;
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  hipError_t alloc(size_t bytes, bool zero = false) {
+    const hipError_t e = hipMalloc(&p, bytes);
+    return e == hipSuccess && zero ? hipMemset(p, 0, bytes) : e;
+  }
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+  ~DeviceBuffer() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+struct Events {
+  hipEvent_t a = nullptr, b = nullptr;
+  hipError_t create() {
+    const hipError_t e = hipEventCreate(&a);
+    return e == hipSuccess ? hipEventCreate(&b) : e;
+  }
+  ~Events() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+};
+
+// Device time of `launch` (kernel launches, or one async copy whose hipError_t it returns) on
+// stream `s`.  Non-zero with the last error set on any HIP failure, the launch's included.
+template <class Launch>
+int timed(const Events& ev, float* ms, Launch&& launch, hipStream_t s = nullptr) {
+  HIP_TRY(hipEventRecord(ev.a, s));
+  if constexpr (std::is_void_v<decltype(launch())>) {
+    launch();
+  } else {
+    HIP_TRY(launch());
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ev.b, s));
+  HIP_TRY(hipEventSynchronize(ev.b));
+  HIP_TRY(hipEventElapsedTime(ms, ev.a, ev.b));
+  return 0;
+}
+
+// A GEMM on caller operands: upload `in`, poison C with 0xFF (NaN: an element the kernel never
+// writes cannot pass), launch(device operands in order, device C), download C.
+struct HostOperand {
+  const void* p;
+  size_t bytes;
+};
+
+template <class Launch>
+int gemm_on_host_operands(std::initializer_list<HostOperand> in, float* c, size_t c_elems, Launch&& launch) {
+  std::vector<DeviceBuffer> d(in.size());
+  std::vector<const void*> dp;
+  for (const HostOperand& h : in) {
+    DeviceBuffer& buf = d[dp.size()];
+    HIP_TRY(buf.alloc(h.bytes));
+    HIP_TRY(hipMemcpy(buf.p, h.p, h.bytes, hipMemcpyHostToDevice));
+    dp.push_back(buf.p);
+  }
+  DeviceBuffer dc;
+  HIP_TRY(dc.alloc(c_elems * 4));
+  HIP_TRY(hipMemset(dc.p, 0xFF, c_elems * 4));
+  launch(dp.data(), dc.as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(c, dc.p, c_elems * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+}  // namespace bgc_diag

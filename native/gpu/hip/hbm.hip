@@ -1,0 +1,388 @@
+// HBM3E bandwidth (bgc_diag_hbm), the address-in-data walk over free VRAM (bgc_diag_hbm_walk)
+// and pinned host<->device copies over PCIe (bgc_diag_pcie).
+//
+// HBM phases are pure streams: 16 B per lane (global_load/store_dwordx4), 256-thread blocks,
+// 8 blocks per CU (2048 WGs >> 256 CUs) each owning one contiguous slab, 4 independent 16 B
+// accesses in flight per lane so each CU keeps ~128 KiB outstanding; nontemporal hints since
+// every byte is touched exactly once per pass.  The bandwidth phases run on two buffers of
+// `bytes` each (the node agent uses 1 GiB, 4x the 256 MiB Infinity Cache, so the rates are
+// HBM rates); coverage of the whole HBM is the job of the separate address-pattern walk over
+// ~all free VRAM (walk_fill / walk_check).
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <utility>
+
+#include "diag_common.h"
+
+namespace {
+
+using namespace bgc_diag;
+
+constexpr int kUnroll = 4;
+
+__device__ __forceinline__ u32x4 pattern16(uint64_t i, uint32_t seed) {
+  uint32_t w = static_cast<uint32_t>(i << 2) ^ static_cast<uint32_t>(i >> 30) * 0x9e3779b9U;
+  u32x4 v;
+  v.x = mix32(w ^ seed);
+  v.y = mix32((w + 1) ^ seed);
+  v.z = mix32((w + 2) ^ seed);
+  v.w = mix32((w + 3) ^ seed);
+  return v;
+}
+
+// Each block streams one contiguous slab (per-block chunking keeps DRAM pages open and
+// measured 5.57 TB/s copy / 6.19 TB/s read on MI355X vs 5.08 / 5.61 for a grid-stride
+// interleave — tools/probes/hbm_sweep.hip, profiles/archive/hbm_sweep_r1.jsonl).  Per step a
+// lane handles kUnroll 16-byte elements kBlock apart and calls consume(i) on each; with kLoad all
+// of them are loaded from src[i] before the first consume(i, value), so a copy keeps kUnroll
+// loads in flight.
+template <bool kLoad, class Consume>
+__device__ __forceinline__ void slab_stream(const u32x4* src, uint64_t n16, Consume consume) {
+  const uint64_t per = (n16 + gridDim.x - 1) / gridDim.x;
+  const uint64_t beg = static_cast<uint64_t>(blockIdx.x) * per;
+  const uint64_t end = beg + per < n16 ? beg + per : n16;
+  for (uint64_t b = beg + threadIdx.x; b < end; b += kBlock * kUnroll) {
+    u32x4 v[kUnroll];
+    if constexpr (kLoad) {
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        const uint64_t i = b + u * kBlock;
+        if (i < end) v[u] = __builtin_nontemporal_load(&src[i]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const uint64_t i = b + u * kBlock;
+      if (i < end) {
+        if constexpr (kLoad) consume(i, v[u]);
+        else consume(i);
+      }
+    }
+  }
+}
+
+// a lane's wrong words and the lowest of them
+struct BadWords {
+  unsigned long long count = 0, first = ~0ULL;
+  __device__ __forceinline__ void add(unsigned long long n, unsigned long long where) {
+    count += n;
+    first = std::min(first, where);
+  }
+  __device__ __forceinline__ void report(unsigned long long* bad, unsigned long long* first_bad) const {
+    if (count) {
+      atomicAdd(bad, count);
+      atomicMin(first_bad, first);
+    }
+  }
+};
+
+__global__ __launch_bounds__(kBlock) void hbm_fill(u32x4* __restrict__ buf, uint64_t n16, uint32_t seed) {
+  slab_stream<false>(nullptr, n16, [=](uint64_t i) { __builtin_nontemporal_store(pattern16(i, seed), &buf[i]); });
+}
+
+__global__ __launch_bounds__(kBlock) void hbm_copy(const u32x4* __restrict__ src, u32x4* __restrict__ dst, uint64_t n16) {
+  slab_stream<true>(src, n16, [=](uint64_t i, const u32x4& v) { __builtin_nontemporal_store(v, &dst[i]); });
+}
+
+__global__ __launch_bounds__(kBlock) void hbm_check(const u32x4* __restrict__ buf, uint64_t n16, uint32_t seed,
+                                                    unsigned long long* __restrict__ bad,
+                                                    unsigned long long* __restrict__ first_bad) {
+  BadWords w;
+  slab_stream<true>(buf, n16, [=, &w](uint64_t i, const u32x4& v) {
+    const u32x4 e = pattern16(i, seed);
+    const int nb = (v.x != e.x) + (v.y != e.y) + (v.z != e.z) + (v.w != e.w);
+    if (nb) w.add(nb, i * 4);
+  });
+  w.report(bad, first_bad);
+}
+
+// ---------------------------------------------------------------------------
+// HBM walk (bgc_diag_hbm_walk): every 64-bit word holds its own device address ^ key.
+// A stuck bit, a weak cell or a write that decodes to the wrong row/bank/stack shows up
+// at verify time as a word whose content is not its address.  The inverse pass is the
+// same kernel with ~key, so every bit is checked at 0 and at 1.
+
+__device__ __forceinline__ u32x4 walk_value(const u32x4* p, uint64_t key) {
+  const uint64_t a = reinterpret_cast<uint64_t>(p);
+  const uint64_t w0 = a ^ key, w1 = (a + 8) ^ key;
+  u32x4 v;
+  v.x = static_cast<uint32_t>(w0);
+  v.y = static_cast<uint32_t>(w0 >> 32);
+  v.z = static_cast<uint32_t>(w1);
+  v.w = static_cast<uint32_t>(w1 >> 32);
+  return v;
+}
+
+__global__ __launch_bounds__(kBlock) void walk_fill(u32x4* __restrict__ buf, uint64_t n16, uint64_t key) {
+  slab_stream<false>(nullptr, n16, [=](uint64_t i) { __builtin_nontemporal_store(walk_value(&buf[i], key), &buf[i]); });
+}
+
+__global__ __launch_bounds__(kBlock) void walk_check(const u32x4* __restrict__ buf, uint64_t n16, uint64_t key,
+                                                     unsigned long long* __restrict__ bad,
+                                                     unsigned long long* __restrict__ first_bad_addr) {
+  BadWords w;
+  slab_stream<true>(buf, n16, [=, &w](uint64_t i, const u32x4& v) {
+    const u32x4 e = walk_value(&buf[i], key);
+    const bool b0 = v.x != e.x || v.y != e.y, b1 = v.z != e.z || v.w != e.w;
+    if (b0 || b1) w.add(static_cast<unsigned long long>(b0) + b1, reinterpret_cast<uint64_t>(&buf[i]) + (b0 ? 0 : 8));
+  });
+  w.report(bad, first_bad_addr);
+}
+
+struct HostBuffer {  // pinned: DMA straight from/to it, no staging copy
+  void* p = nullptr;
+  ~HostBuffer() {
+    if (p) (void)hipHostFree(p);
+  }
+};
+
+struct Streams {
+  hipStream_t a = nullptr, b = nullptr;
+  hipError_t create() {
+    const hipError_t e = hipStreamCreateWithFlags(&a, hipStreamNonBlocking);
+    return e == hipSuccess ? hipStreamCreateWithFlags(&b, hipStreamNonBlocking) : e;
+  }
+  ~Streams() {
+    if (a) (void)hipStreamDestroy(a);
+    if (b) (void)hipStreamDestroy(b);
+  }
+};
+
+struct Chunks {  // the HBM walk's allocations, freed on every exit path
+  std::vector<std::pair<void*, uint64_t>> v;
+  ~Chunks() {
+    for (auto& c : v) (void)hipFree(c.first);
+  }
+};
+
+// {bad words, first bad} counters of the check kernels
+int reset_counters(unsigned long long* bad) {
+  const unsigned long long init[2] = {0ULL, ~0ULL};
+  HIP_TRY(hipMemcpy(bad, init, sizeof(init), hipMemcpyHostToDevice));
+  return 0;
+}
+
+uint64_t mix64(uint64_t x) {
+  x ^= x >> 33;
+  x *= 0xff51afd7ed558ccdULL;
+  x ^= x >> 33;
+  x *= 0xc4ceb9fe1a85ec53ULL;
+  x ^= x >> 33;
+  return x;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bgc_diag_hbm(int device, uint64_t bytes, int iters, uint32_t seed, bgc_hbm_result* out) {
+  if (!out || iters <= 0 || bytes < (1u << 20)) {
+    g_last_error = "invalid arguments";
+    return 1;
+  }
+  std::memset(out, 0, sizeof(*out));
+  bytes &= ~static_cast<uint64_t>(15);
+  const uint64_t n16 = bytes / 16;
+  HIP_TRY(hipSetDevice(device));
+  DeviceBuffer a, b, counters;
+  HIP_TRY(a.alloc(bytes));
+  HIP_TRY(b.alloc(bytes));
+  HIP_TRY(counters.alloc(2 * sizeof(unsigned long long)));
+  auto* bad = counters.as<unsigned long long>();
+  if (reset_counters(bad) != 0) return 1;
+  const dim3 grid(cu_count(device) * 8), block(kBlock);
+  Events ev;
+  HIP_TRY(ev.create());
+  float best_fill = 1e30f, best_copy = 1e30f, best_check = 1e30f, total = 0.f;
+  auto fill = [&] { hipLaunchKernelGGL(hbm_fill, grid, block, 0, nullptr, a.as<u32x4>(), n16, seed); };
+  auto copy = [&] { hipLaunchKernelGGL(hbm_copy, grid, block, 0, nullptr, a.as<const u32x4>(), b.as<u32x4>(), n16); };
+  auto check = [&] { hipLaunchKernelGGL(hbm_check, grid, block, 0, nullptr, b.as<const u32x4>(), n16, seed, bad, bad + 1); };
+  auto phase = [&](auto& launch, float* best) {
+    float ms = 0.f;
+    if (timed(ev, &ms, launch) != 0) return 1;
+    *best = std::min(*best, ms);
+    total += ms;
+    return 0;
+  };
+  fill();  // warm-up (also first-touch of the pages)
+  HIP_TRY(hipGetLastError());
+  for (int it = 0; it < iters; ++it) {
+    if (phase(fill, &best_fill) != 0 || phase(copy, &best_copy) != 0 || phase(check, &best_check) != 0) return 1;
+  }
+  unsigned long long res[2];
+  HIP_TRY(hipMemcpy(res, bad, sizeof(res), hipMemcpyDeviceToHost));
+  out->bytes = bytes;
+  out->iters = iters;
+  out->write_gbps = static_cast<double>(bytes) / (best_fill * 1e-3) / 1e9;
+  out->copy_gbps = 2.0 * static_cast<double>(bytes) / (best_copy * 1e-3) / 1e9;
+  out->read_gbps = static_cast<double>(bytes) / (best_check * 1e-3) / 1e9;
+  out->mismatches = res[0];
+  out->first_bad_word = res[1];
+  out->elapsed_ms = total;
+  return 0;
+}
+
+int bgc_diag_hbm_walk(int device, double fraction, uint64_t chunk_bytes, int budget_ms, uint32_t seed,
+                      bgc_hbm_walk_result* out) {
+  constexpr uint64_t kMinChunk = 64ULL << 20;
+  if (!out || !(fraction > 0.0 && fraction <= 0.99) || chunk_bytes < kMinChunk || budget_ms <= 0) {
+    g_last_error = "invalid arguments: 0 < fraction <= 0.99, chunk_bytes >= 64 MiB, budget_ms > 0";
+    return 1;
+  }
+  std::memset(out, 0, sizeof(*out));
+  const auto t0 = std::chrono::steady_clock::now();
+  auto elapsed_ms = [&] {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  };
+  HIP_TRY(hipSetDevice(device));
+  DeviceBuffer counters;  // before the walk takes the memory
+  HIP_TRY(counters.alloc(2 * sizeof(unsigned long long)));
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  out->free_bytes = free_b;
+  out->total_bytes = total_b;
+  const uint64_t align = 2ULL << 20;
+  const uint64_t target = static_cast<uint64_t>(fraction * static_cast<double>(free_b)) & ~(align - 1);
+  out->target_bytes = target;
+  Chunks chunks;
+  uint64_t got = 0, cb = chunk_bytes & ~(align - 1);
+  while (got < target) {
+    const uint64_t want = std::min(cb, target - got);
+    void* p = nullptr;
+    if (hipMalloc(&p, want) != hipSuccess || !p) {
+      (void)hipGetLastError();  // clear the sticky allocation error
+      if (cb <= kMinChunk) break;
+      cb = std::max(kMinChunk, (cb / 2) & ~(align - 1));
+      continue;
+    }
+    chunks.v.emplace_back(p, want);
+    got += want;
+  }
+  if (chunks.v.empty()) {
+    g_last_error = "hbm walk: no device memory could be allocated";
+    return 1;
+  }
+  out->chunks = static_cast<int>(chunks.v.size());
+  out->alloc_ms = elapsed_ms();
+  auto* bad = counters.as<unsigned long long>();
+  const dim3 grid(cu_count(device) * 8), block(kBlock);
+  Events ev;
+  HIP_TRY(ev.create());
+  const uint64_t key0 = mix64(0x9e3779b97f4a7c15ULL ^ seed);
+  double fill_ms = 0, check_ms = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass > 0 && elapsed_ms() > budget_ms) {
+      out->budget_hit = 1;
+      break;
+    }
+    const uint64_t key = pass == 0 ? key0 : ~key0;
+    if (reset_counters(bad) != 0) return 1;
+    float ms = 0.f;
+    if (timed(ev, &ms, [&] {
+          for (const auto& c : chunks.v) {
+            hipLaunchKernelGGL(walk_fill, grid, block, 0, nullptr, static_cast<u32x4*>(c.first), c.second / 16, key);
+          }
+        }) != 0) {
+      return 1;
+    }
+    fill_ms += ms;
+    if (timed(ev, &ms, [&] {
+          for (const auto& c : chunks.v) {
+            hipLaunchKernelGGL(walk_check, grid, block, 0, nullptr, static_cast<const u32x4*>(c.first), c.second / 16, key,
+                               bad, bad + 1);
+          }
+        }) != 0) {
+      return 1;
+    }
+    check_ms += ms;
+    unsigned long long res[2];
+    HIP_TRY(hipMemcpy(res, bad, sizeof(res), hipMemcpyDeviceToHost));
+    if (res[0] && !out->mismatches) {  // the first failing pass names the first bad word
+      out->first_bad_addr = res[1];
+      uint64_t found = 0;
+      HIP_TRY(hipMemcpy(&found, reinterpret_cast<void*>(static_cast<uintptr_t>(res[1])), 8, hipMemcpyDeviceToHost));
+      out->first_bad_xor = found ^ (static_cast<uint64_t>(res[1]) ^ key);
+    }
+    out->mismatches += res[0];
+    out->passes = pass + 1;
+  }
+  out->bytes_covered = got;
+  const double moved = static_cast<double>(got) * out->passes;
+  out->write_gbps = fill_ms > 0 ? moved / (fill_ms * 1e-3) / 1e9 : 0.0;
+  out->read_gbps = check_ms > 0 ? moved / (check_ms * 1e-3) / 1e9 : 0.0;
+  out->elapsed_ms = elapsed_ms();
+  return 0;
+}
+
+int bgc_diag_pcie(int device, uint64_t bytes, int iters, uint32_t seed, bgc_pcie_result* out) {
+  if (!out || iters <= 0 || bytes < (1u << 20) || bytes > (uint64_t{16} << 30)) {
+    g_last_error = "invalid arguments";
+    return 1;
+  }
+  std::memset(out, 0, sizeof(*out));
+  bytes &= ~static_cast<uint64_t>(7);
+  const uint64_t words = bytes / 8;
+  HIP_TRY(hipSetDevice(device));
+  HostBuffer src, dst, src2;
+  DeviceBuffer d1, d2;
+  HIP_TRY(hipHostMalloc(&src.p, bytes, hipHostMallocDefault));
+  HIP_TRY(hipHostMalloc(&dst.p, bytes, hipHostMallocDefault));
+  HIP_TRY(hipHostMalloc(&src2.p, bytes, hipHostMallocDefault));
+  HIP_TRY(d1.alloc(bytes));
+  HIP_TRY(d2.alloc(bytes));
+  auto* s64 = static_cast<uint64_t*>(src.p);
+  for (uint64_t i = 0; i < words; ++i) s64[i] = (static_cast<uint64_t>(mix32(static_cast<uint32_t>(i) ^ seed)) << 32) | mix32(static_cast<uint32_t>(i >> 32) + seed + 1);
+  std::memset(dst.p, 0, bytes);
+  std::memset(src2.p, 0x5a, bytes);
+  Streams st;
+  HIP_TRY(st.create());
+  Events ev, ev2;
+  HIP_TRY(ev.create());
+  HIP_TRY(ev2.create());
+  // warm-up both directions (page tables, DMA engine clocks)
+  HIP_TRY(hipMemcpyAsync(d1.p, src.p, bytes, hipMemcpyHostToDevice, st.a));
+  HIP_TRY(hipMemcpyAsync(d2.p, d1.p, bytes, hipMemcpyDeviceToDevice, st.a));
+  HIP_TRY(hipMemcpyAsync(dst.p, d2.p, bytes, hipMemcpyDeviceToHost, st.a));
+  HIP_TRY(hipStreamSynchronize(st.a));
+  // round trip check: the pattern went host -> device -> device -> host
+  const auto* d64 = static_cast<const uint64_t*>(dst.p);
+  uint64_t bad = 0;
+  for (uint64_t i = 0; i < words; ++i) bad += d64[i] != s64[i];
+  float best_h2d = 1e30f, best_d2h = 1e30f, ms = 0.f, total = 0.f;
+  double best_bidir = 0;
+  for (int it = 0; it < iters; ++it) {
+    if (timed(ev, &ms, [&] { return hipMemcpyAsync(d1.p, src.p, bytes, hipMemcpyHostToDevice, st.a); }, st.a) != 0) return 1;
+    best_h2d = std::min(best_h2d, ms);
+    total += ms;
+    if (timed(ev, &ms, [&] { return hipMemcpyAsync(dst.p, d1.p, bytes, hipMemcpyDeviceToHost, st.a); }, st.a) != 0) return 1;
+    best_d2h = std::min(best_d2h, ms);
+    total += ms;
+    // both directions at once: H2D on one stream, D2H on the other
+    HIP_TRY(hipEventRecord(ev.a, st.a));
+    HIP_TRY(hipEventRecord(ev2.a, st.b));
+    HIP_TRY(hipMemcpyAsync(d2.p, src2.p, bytes, hipMemcpyHostToDevice, st.a));
+    HIP_TRY(hipMemcpyAsync(dst.p, d1.p, bytes, hipMemcpyDeviceToHost, st.b));
+    HIP_TRY(hipEventRecord(ev.b, st.a));
+    HIP_TRY(hipEventRecord(ev2.b, st.b));
+    HIP_TRY(hipEventSynchronize(ev.b));
+    HIP_TRY(hipEventSynchronize(ev2.b));
+    float ms_a = 0.f, ms_b = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms_a, ev.a, ev.b));
+    HIP_TRY(hipEventElapsedTime(&ms_b, ev2.a, ev2.b));
+    const double span = std::max(ms_a, ms_b);
+    best_bidir = std::max(best_bidir, 2.0 * static_cast<double>(bytes) / (span * 1e-3) / 1e9);
+    total += static_cast<float>(span);
+  }
+  HIP_TRY(hipGetLastError());
+  out->bytes = bytes;
+  out->iters = iters;
+  out->h2d_gbps = static_cast<double>(bytes) / (best_h2d * 1e-3) / 1e9;
+  out->d2h_gbps = static_cast<double>(bytes) / (best_d2h * 1e-3) / 1e9;
+  out->bidir_gbps = best_bidir;
+  out->mismatches = bad;
+  out->elapsed_ms = total;
+  return 0;
+}
+
+}  // extern "C"

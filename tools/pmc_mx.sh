@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # PMC counters (counters only, no trace domains) of the register-operand matrix-core
-# kernels: bf16 mfma_throughput and the MX fp8/fp4 mfma_lowp_throughput, as the node
+# kernels: mfma_throughput<Bf16Tile> and the MX fp8/fp4 mfma_throughput<MxTile<fmt>>, as the node
 # agent's check runs them (ops.mfma_lowp, ops.mfma).  One rocprofv3 pass.
 #   OUT=gpurun_out/pmc_mx bash tools/pmc_mx.sh
 set -o pipefail

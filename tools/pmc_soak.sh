@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # PMC counters (counters only, no trace domains) of the 256x256 soak kernels at 8192^3:
 # BGC_SOAK_KERNEL values in $KERNELS (default "2buf pingpong"), one rocprofv3 pass each.
-#   OUT=gpurun_out/pmc_soak [KERNELS="pingpong0 pingpong"] bash tools/pmc_soak.sh
+#   [OUT=<dir>] [KERNELS="pingpong"] bash tools/pmc_soak.sh
 set -o pipefail
 OUT=${OUT:-gpurun_out/pmc_soak}
 rm -rf "$OUT" && mkdir -p "$OUT"
