@@ -21,6 +21,9 @@ These are the only compute kernels in the framework: the reference controller ha
   operand/scale layout against an independent PyTorch decode
 * ``pcie(device)``      — host<->device copy bandwidth, pinned
 * ``device_bdf(device)``— the HIP device's PCI address, to match it to amdsmi / kubelet
+* ``hbm_planted``, ``hbm_walk_planted``, ``pcie_planted``, ``mfma_planted``,
+  ``mfma_lowp_planted``, ``gemm_soak_planted`` — for tests: the same diagnostics with wrong
+  values planted in their own data, to show that they are detected (see below)
 
 All fail loudly (RuntimeError) if ``libbgc_gpu_diag.so`` or the GPU is missing; there
 is no CPU fallback.
@@ -76,6 +79,60 @@ def gemm_soak(device=0, m=8192, n=8192, k=8192, launches=10, seed=0x5EED):
 
 def pcie(device=0, nbytes=256 << 20, iters=5, seed=0x5EED):
     return json.loads(native().diag_pcie(device, nbytes, iters, seed))
+
+
+# ---------------------------------------------------------------------------------------------
+# Planted variants, for tests only: the same diagnostics with deliberately wrong values written
+# into their own buffers or accumulators between the phase that produces the data and the phase
+# that checks it, to show that a wrong value reaches the counters.  Plants are lists of tuples; an
+# empty list is the production run.  A plant outside the buffer (or a wave, lane, round or index out
+# of range) is refused with "invalid arguments" before the GPU is touched.  Neither the node agent
+# nor judge can ask for a plant.
+
+ALL_WAVES = -1  # `wave` of a check-phase plant: every wave
+
+_LOWP_VARIANTS = {"fp8": 0, "fp8_scaled": 1, "fp4": 2, "fp4_scaled": 3}
+_LOWP_FORMATS = {"fp8": 0, "fp4": 1}
+
+
+def hbm_planted(nbytes, plants, device=0, seed=0x5EED):
+    """One fill, copy and check with `plants` = [(32-bit word index, xor mask), ...] applied to
+    the copy before the check.  The rates are those of one cold iteration: no measurement."""
+    return json.loads(native().diag_hbm_planted(device, nbytes, seed, list(plants)))
+
+
+def hbm_walk_planted(nbytes, chunk_bytes, plants, device=0, seed=0x5EED):
+    """The walk over `nbytes` in chunks of `chunk_bytes` with `plants` = [(pass, chunk, 64-bit
+    word offset in the chunk, xor mask), ...] applied after that pass's fill.  The result also
+    lists the chunks as ``chunk_list`` = [[device address, bytes], ...]."""
+    return json.loads(native().diag_hbm_walk_planted(device, nbytes, chunk_bytes, seed, list(plants)))
+
+
+def pcie_planted(nbytes, plants, device=0, seed=0x5EED):
+    """The round trip with `plants` = [(64-bit word index, xor mask), ...] applied to the device
+    buffer between the upload and the copies back."""
+    return json.loads(native().diag_pcie_planted(device, nbytes, seed, list(plants)))
+
+
+def mfma_planted(check_plants, rate_plants=(), device=0, waves_per_cu=1, iters=64, seed=0x5EED):
+    """`check_plants` = [(wave or ALL_WAVES, round, lane, i, delta), ...] add delta to acc[i] of
+    that lane before the comparison; `rate_plants` = [(wave, lane, chain, i, delta), ...] do so
+    after the throughput loop."""
+    return json.loads(native().diag_mfma_planted(device, waves_per_cu, iters, seed, list(check_plants), list(rate_plants)))
+
+
+def mfma_lowp_planted(check_plants, rate_plants=(), device=0, waves_per_cu=1, iters=64, seed=0x5EED):
+    """As mfma_planted, with the variant ("fp8", "fp8_scaled", "fp4", "fp4_scaled") in front of a
+    check plant and the format ("fp8", "fp4") in front of a rate plant."""
+    check = [(_LOWP_VARIANTS[p[0]],) + tuple(p[1:]) for p in check_plants]
+    rate = [(_LOWP_FORMATS[p[0]],) + tuple(p[1:]) for p in rate_plants]
+    return json.loads(native().diag_mfma_lowp_planted(device, waves_per_cu, iters, seed, check, rate))
+
+
+def gemm_soak_planted(m, n, k, launches, plants, device=0, seed=0x5EED):
+    """`plants` = [(launch, row, col, delta), ...] add delta to C[row][col] after that launch and
+    before its checksums; only the first and the last launch are checked."""
+    return json.loads(native().diag_gemm_soak_planted(device, m, n, k, launches, seed, list(plants)))
 
 
 def _bf16_bytes(x):

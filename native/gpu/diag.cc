@@ -55,12 +55,19 @@ Diag::Diag(const std::string& path) : path_(path) {
   BGC_DIAG_SYM(mx_gemm_, bgc_diag_mx_gemm);
   BGC_DIAG_SYM(walk_, bgc_diag_hbm_walk);
   BGC_DIAG_SYM(bdf_, bgc_diag_device_bdf);
+  BGC_DIAG_SYM(hbm_planted_, bgc_diag_hbm_planted);
+  BGC_DIAG_SYM(walk_planted_, bgc_diag_hbm_walk_planted);
+  BGC_DIAG_SYM(pcie_planted_, bgc_diag_pcie_planted);
+  BGC_DIAG_SYM(mfma_planted_, bgc_diag_mfma_planted);
+  BGC_DIAG_SYM(lowp_planted_, bgc_diag_mfma_lowp_planted);
+  BGC_DIAG_SYM(soak_planted_, bgc_diag_gemm_soak_planted);
   BGC_DIAG_SYM(last_error_, bgc_diag_last_error);
   decltype(&bgc_diag_abi_version) abi = nullptr;
   BGC_DIAG_SYM(abi, bgc_diag_abi_version);
 #undef BGC_DIAG_SYM
   if (!device_count_ || !hbm_ || !mfma_ || !lowp_ || !arch_ || !gemm_ || !burn_ || !pcie_ || !soak_ || !tiled_ ||
-      !mx_gemm_ || !walk_ || !bdf_ || !last_error_ || !abi ||
+      !mx_gemm_ || !walk_ || !bdf_ || !hbm_planted_ || !walk_planted_ || !pcie_planted_ || !mfma_planted_ ||
+      !lowp_planted_ || !soak_planted_ || !last_error_ || !abi ||
       abi() != BGC_DIAG_ABI_VERSION) {
     throw std::runtime_error(path + " is not a compatible bgc diag library");
   }
@@ -98,9 +105,10 @@ std::string Diag::device_arch(int device) {
   return buf;
 }
 
-json::Value Diag::hbm(int device, uint64_t bytes, int iters, uint32_t seed) {
-  bgc_hbm_result r{};
-  if (hbm_(device, bytes, iters, seed, &r) != 0) throw std::runtime_error(std::string("hbm diag: ") + last_error_());
+namespace {
+
+// The result structs as JSON: one shape for a diagnostic and its planted variant.
+json::Value hbm_json(int device, const bgc_hbm_result& r) {
   json::Value v = json::Value::object();
   v["device"] = device;
   v["bytes"] = static_cast<unsigned long long>(r.bytes);
@@ -115,11 +123,7 @@ json::Value Diag::hbm(int device, uint64_t bytes, int iters, uint32_t seed) {
   return v;
 }
 
-json::Value Diag::mfma(int device, int waves_per_cu, int throughput_iters, uint32_t seed) {
-  bgc_mfma_result r{};
-  if (mfma_(device, waves_per_cu, throughput_iters, seed, &r) != 0) {
-    throw std::runtime_error(std::string("mfma diag: ") + last_error_());
-  }
+json::Value mfma_json(int device, const bgc_mfma_result& r) {
   json::Value v = json::Value::object();
   v["device"] = device;
   v["tiles_checked"] = static_cast<unsigned long long>(r.tiles_checked);
@@ -145,11 +149,7 @@ json::Value Diag::mfma(int device, int waves_per_cu, int throughput_iters, uint3
   return v;
 }
 
-json::Value Diag::mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint32_t seed) {
-  bgc_lowp_result r{};
-  if (lowp_(device, waves_per_cu, throughput_iters, seed, &r) != 0) {
-    throw std::runtime_error(std::string("low-precision mfma diag: ") + last_error_());
-  }
+json::Value lowp_json(int device, const bgc_lowp_result& r) {
   json::Value bad = json::Value::array();
   for (int i = 0; i < r.bad_cus && i < 64; ++i) bad.push_back(r.bad_cu_keys[i]);
   const uint64_t mism = r.fp8_mismatches + r.fp8_scaled_mismatches + r.fp4_mismatches + r.fp4_scaled_mismatches;
@@ -170,6 +170,138 @@ json::Value Diag::mfma_lowp(int device, int waves_per_cu, int throughput_iters, 
                               {"passed", mism == 0 && r.throughput_ok != 0}});
 }
 
+json::Value pcie_json(int device, const bgc_pcie_result& r) {
+  return json::Value::object({{"device", device}, {"bytes", static_cast<unsigned long long>(r.bytes)},
+                              {"iters", r.iters}, {"h2d_gbps", r.h2d_gbps}, {"d2h_gbps", r.d2h_gbps},
+                              {"bidir_gbps", r.bidir_gbps}, {"mismatches", static_cast<unsigned long long>(r.mismatches)},
+                              {"elapsed_ms", r.elapsed_ms}, {"passed", r.mismatches == 0}});
+}
+
+json::Value soak_json(int device, const bgc_soak_result& r) {
+  return json::Value::object({{"device", device}, {"m", r.m}, {"n", r.n}, {"k", r.k}, {"launches", r.launches},
+                              {"tile", r.tile}, {"kernel", r.kernel == 2 ? "pingpong" : "2buf"},
+                              {"elapsed_ms", r.elapsed_ms}, {"tflops_mean", r.tflops_mean},
+                              {"tflops_best", r.tflops_best},
+                              {"row_mismatches", static_cast<unsigned long long>(r.row_mismatches)},
+                              {"col_mismatches", static_cast<unsigned long long>(r.col_mismatches)},
+                              {"passed", r.row_mismatches == 0 && r.col_mismatches == 0}});
+}
+
+json::Value walk_json(int device, const bgc_hbm_walk_result& r) {
+  char addr[32], flips[32];
+  std::snprintf(addr, sizeof(addr), "0x%llx", static_cast<unsigned long long>(r.first_bad_addr));
+  std::snprintf(flips, sizeof(flips), "0x%016llx", static_cast<unsigned long long>(r.first_bad_xor));
+  const double cov = r.free_bytes ? static_cast<double>(r.bytes_covered) / static_cast<double>(r.free_bytes) : 0.0;
+  return json::Value::object({{"device", device},
+                              {"free_bytes", static_cast<unsigned long long>(r.free_bytes)},
+                              {"total_bytes", static_cast<unsigned long long>(r.total_bytes)},
+                              {"target_bytes", static_cast<unsigned long long>(r.target_bytes)},
+                              {"bytes_covered", static_cast<unsigned long long>(r.bytes_covered)},
+                              {"coverage_of_free", cov},
+                              {"chunks", r.chunks},
+                              {"passes", r.passes},
+                              {"mismatches", static_cast<unsigned long long>(r.mismatches)},
+                              {"first_bad_addr", r.mismatches ? json::Value(std::string(addr)) : json::Value()},
+                              {"first_bad_bits", r.mismatches ? json::Value(std::string(flips)) : json::Value()},
+                              {"write_gbps", r.write_gbps},
+                              {"read_gbps", r.read_gbps},
+                              {"alloc_ms", r.alloc_ms},
+                              {"elapsed_ms", r.elapsed_ms},
+                              {"budget_hit", r.budget_hit != 0},
+                              {"passed", r.mismatches == 0 && r.passes == 2}});
+}
+
+}  // namespace
+
+json::Value Diag::hbm(int device, uint64_t bytes, int iters, uint32_t seed) {
+  bgc_hbm_result r{};
+  if (hbm_(device, bytes, iters, seed, &r) != 0) throw std::runtime_error(std::string("hbm diag: ") + last_error_());
+  return hbm_json(device, r);
+}
+
+json::Value Diag::mfma(int device, int waves_per_cu, int throughput_iters, uint32_t seed) {
+  bgc_mfma_result r{};
+  if (mfma_(device, waves_per_cu, throughput_iters, seed, &r) != 0) {
+    throw std::runtime_error(std::string("mfma diag: ") + last_error_());
+  }
+  return mfma_json(device, r);
+}
+
+json::Value Diag::mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint32_t seed) {
+  bgc_lowp_result r{};
+  if (lowp_(device, waves_per_cu, throughput_iters, seed, &r) != 0) {
+    throw std::runtime_error(std::string("low-precision mfma diag: ") + last_error_());
+  }
+  return lowp_json(device, r);
+}
+
+// Planted variants (gpu_diag.h): for tests only.
+json::Value Diag::hbm_planted(int device, uint64_t bytes, uint32_t seed, const std::vector<bgc_hbm_plant>& plants) {
+  bgc_hbm_result r{};
+  if (hbm_planted_(device, bytes, seed, plants.data(), static_cast<int>(plants.size()), &r) != 0) {
+    throw std::runtime_error(std::string("hbm diag: ") + last_error_());
+  }
+  return hbm_json(device, r);
+}
+
+json::Value Diag::hbm_walk_planted(int device, uint64_t bytes, uint64_t chunk_bytes, uint32_t seed,
+                                   const std::vector<bgc_walk_plant>& plants) {
+  bgc_hbm_walk_result r{};
+  std::vector<bgc_walk_chunk> chunks(1024);
+  if (walk_planted_(device, bytes, chunk_bytes, seed, plants.data(), static_cast<int>(plants.size()), chunks.data(),
+                    static_cast<int>(chunks.size()), &r) != 0) {
+    throw std::runtime_error(std::string("hbm walk: ") + last_error_());
+  }
+  json::Value v = walk_json(device, r);
+  json::Value list = json::Value::array();
+  for (int c = 0; c < r.chunks && c < static_cast<int>(chunks.size()); ++c) {
+    json::Value one = json::Value::array();
+    one.push_back(static_cast<unsigned long long>(chunks[static_cast<size_t>(c)].base));
+    one.push_back(static_cast<unsigned long long>(chunks[static_cast<size_t>(c)].bytes));
+    list.push_back(one);
+  }
+  v["chunk_list"] = list;
+  return v;
+}
+
+json::Value Diag::pcie_planted(int device, uint64_t bytes, uint32_t seed, const std::vector<bgc_pcie_plant>& plants) {
+  bgc_pcie_result r{};
+  if (pcie_planted_(device, bytes, seed, plants.data(), static_cast<int>(plants.size()), &r) != 0) {
+    throw std::runtime_error(std::string("pcie diag: ") + last_error_());
+  }
+  return pcie_json(device, r);
+}
+
+json::Value Diag::mfma_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
+                               const std::vector<bgc_mfma_check_plant>& check, const std::vector<bgc_mfma_rate_plant>& rate) {
+  bgc_mfma_result r{};
+  if (mfma_planted_(device, waves_per_cu, throughput_iters, seed, check.data(), static_cast<int>(check.size()), rate.data(),
+                    static_cast<int>(rate.size()), &r) != 0) {
+    throw std::runtime_error(std::string("mfma diag: ") + last_error_());
+  }
+  return mfma_json(device, r);
+}
+
+json::Value Diag::mfma_lowp_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
+                                    const std::vector<bgc_lowp_check_plant>& check,
+                                    const std::vector<bgc_lowp_rate_plant>& rate) {
+  bgc_lowp_result r{};
+  if (lowp_planted_(device, waves_per_cu, throughput_iters, seed, check.data(), static_cast<int>(check.size()), rate.data(),
+                    static_cast<int>(rate.size()), &r) != 0) {
+    throw std::runtime_error(std::string("low-precision mfma diag: ") + last_error_());
+  }
+  return lowp_json(device, r);
+}
+
+json::Value Diag::gemm_soak_planted(int device, int m, int n, int k, int launches, uint32_t seed,
+                                    const std::vector<bgc_soak_plant>& plants) {
+  bgc_soak_result r{};
+  if (soak_planted_(device, m, n, k, launches, seed, plants.data(), static_cast<int>(plants.size()), &r) != 0) {
+    throw std::runtime_error(std::string("gemm soak: ") + last_error_());
+  }
+  return soak_json(device, r);
+}
+
 json::Value Diag::burn(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype) {
   bgc_burn_result r{};
   if (burn_(device, duration_ms, waves_per_cu, seed, dtype, &r) != 0) {
@@ -186,22 +318,13 @@ json::Value Diag::burn(int device, int duration_ms, int waves_per_cu, uint32_t s
 json::Value Diag::pcie(int device, uint64_t bytes, int iters, uint32_t seed) {
   bgc_pcie_result r{};
   if (pcie_(device, bytes, iters, seed, &r) != 0) throw std::runtime_error(std::string("pcie diag: ") + last_error_());
-  return json::Value::object({{"device", device}, {"bytes", static_cast<unsigned long long>(r.bytes)},
-                              {"iters", r.iters}, {"h2d_gbps", r.h2d_gbps}, {"d2h_gbps", r.d2h_gbps},
-                              {"bidir_gbps", r.bidir_gbps}, {"mismatches", static_cast<unsigned long long>(r.mismatches)},
-                              {"elapsed_ms", r.elapsed_ms}, {"passed", r.mismatches == 0}});
+  return pcie_json(device, r);
 }
 
 json::Value Diag::gemm_soak(int device, int m, int n, int k, int launches, uint32_t seed) {
   bgc_soak_result r{};
   if (soak_(device, m, n, k, launches, seed, &r) != 0) throw std::runtime_error(std::string("gemm soak: ") + last_error_());
-  return json::Value::object({{"device", device}, {"m", r.m}, {"n", r.n}, {"k", r.k}, {"launches", r.launches},
-                              {"tile", r.tile}, {"kernel", r.kernel == 2 ? "pingpong" : "2buf"},
-                              {"elapsed_ms", r.elapsed_ms}, {"tflops_mean", r.tflops_mean},
-                              {"tflops_best", r.tflops_best},
-                              {"row_mismatches", static_cast<unsigned long long>(r.row_mismatches)},
-                              {"col_mismatches", static_cast<unsigned long long>(r.col_mismatches)},
-                              {"passed", r.row_mismatches == 0 && r.col_mismatches == 0}});
+  return soak_json(device, r);
 }
 
 void Diag::gemm(int device, int m, int n, int k, const uint16_t* a, const uint16_t* b, float* c) {
@@ -224,27 +347,7 @@ json::Value Diag::hbm_walk(int device, double fraction, uint64_t chunk_bytes, in
   if (walk_(device, fraction, chunk_bytes, budget_ms, seed, &r) != 0) {
     throw std::runtime_error(std::string("hbm walk: ") + last_error_());
   }
-  char addr[32], flips[32];
-  std::snprintf(addr, sizeof(addr), "0x%llx", static_cast<unsigned long long>(r.first_bad_addr));
-  std::snprintf(flips, sizeof(flips), "0x%016llx", static_cast<unsigned long long>(r.first_bad_xor));
-  const double cov = r.free_bytes ? static_cast<double>(r.bytes_covered) / static_cast<double>(r.free_bytes) : 0.0;
-  return json::Value::object({{"device", device},
-                              {"free_bytes", static_cast<unsigned long long>(r.free_bytes)},
-                              {"total_bytes", static_cast<unsigned long long>(r.total_bytes)},
-                              {"target_bytes", static_cast<unsigned long long>(r.target_bytes)},
-                              {"bytes_covered", static_cast<unsigned long long>(r.bytes_covered)},
-                              {"coverage_of_free", cov},
-                              {"chunks", r.chunks},
-                              {"passes", r.passes},
-                              {"mismatches", static_cast<unsigned long long>(r.mismatches)},
-                              {"first_bad_addr", r.mismatches ? json::Value(std::string(addr)) : json::Value()},
-                              {"first_bad_bits", r.mismatches ? json::Value(std::string(flips)) : json::Value()},
-                              {"write_gbps", r.write_gbps},
-                              {"read_gbps", r.read_gbps},
-                              {"alloc_ms", r.alloc_ms},
-                              {"elapsed_ms", r.elapsed_ms},
-                              {"budget_hit", r.budget_hit != 0},
-                              {"passed", r.mismatches == 0 && r.passes == 2}});
+  return walk_json(device, r);
 }
 
 std::string Diag::device_bdf(int device) {

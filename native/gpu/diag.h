@@ -3,6 +3,7 @@
 
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "core/json.h"
 #include "gpu/hip/gpu_diag.h"
@@ -89,6 +90,20 @@ class Diag {
                const uint8_t* bt_scales, float* c);
   // Address-pattern walk of `fraction` of the free VRAM (see bgc_diag_hbm_walk).
   json::Value hbm_walk(int device, double fraction, uint64_t chunk_bytes, int budget_ms, uint32_t seed);
+  // Planted variants, for tests only (gpu_diag.h): the diagnostics above with wrong values
+  // written into their own data before the check, to show that they are detected.  Same JSON
+  // as the production calls (hbm_walk_planted adds "chunk_list": [[device address, bytes], ...]).
+  // Nothing in the node agent or the diag worker calls them.
+  json::Value hbm_planted(int device, uint64_t bytes, uint32_t seed, const std::vector<bgc_hbm_plant>& plants);
+  json::Value hbm_walk_planted(int device, uint64_t bytes, uint64_t chunk_bytes, uint32_t seed,
+                               const std::vector<bgc_walk_plant>& plants);
+  json::Value pcie_planted(int device, uint64_t bytes, uint32_t seed, const std::vector<bgc_pcie_plant>& plants);
+  json::Value mfma_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
+                           const std::vector<bgc_mfma_check_plant>& check, const std::vector<bgc_mfma_rate_plant>& rate);
+  json::Value mfma_lowp_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
+                                const std::vector<bgc_lowp_check_plant>& check, const std::vector<bgc_lowp_rate_plant>& rate);
+  json::Value gemm_soak_planted(int device, int m, int n, int k, int launches, uint32_t seed,
+                                const std::vector<bgc_soak_plant>& plants);
   // PCI bus id of a HIP device, lower-case ("0000:05:00.0").
   std::string device_bdf(int device);
   const std::string& path() const { return path_; }
@@ -110,6 +125,12 @@ class Diag {
   decltype(&bgc_diag_mx_gemm) mx_gemm_ = nullptr;
   decltype(&bgc_diag_hbm_walk) walk_ = nullptr;
   decltype(&bgc_diag_device_bdf) bdf_ = nullptr;
+  decltype(&bgc_diag_hbm_planted) hbm_planted_ = nullptr;
+  decltype(&bgc_diag_hbm_walk_planted) walk_planted_ = nullptr;
+  decltype(&bgc_diag_pcie_planted) pcie_planted_ = nullptr;
+  decltype(&bgc_diag_mfma_planted) mfma_planted_ = nullptr;
+  decltype(&bgc_diag_mfma_lowp_planted) lowp_planted_ = nullptr;
+  decltype(&bgc_diag_gemm_soak_planted) soak_planted_ = nullptr;
   decltype(&bgc_diag_last_error) last_error_ = nullptr;
 };
 

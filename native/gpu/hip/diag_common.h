@@ -91,6 +91,22 @@ int timed(const Events& ev, float* ms, Launch&& launch, hipStream_t s = nullptr)
   return 0;
 }
 
+// Test plants (gpu_diag.h, "planted variants").  A plant list is `n` entries at `plants`.
+inline bool plant_list_ok(const void* plants, int n) {
+  return n >= 0 && n <= BGC_DIAG_MAX_PLANTS && (n == 0 || plants);
+}
+
+// *p = f(*p) on one value in device memory: a host read-modify-write on the null stream, so it is
+// ordered after the null-stream kernels that produced the data and before those that check it.
+template <class T, class F>
+int modify_device_value(T* p, F&& f) {
+  T v;
+  HIP_TRY(hipMemcpy(&v, p, sizeof(v), hipMemcpyDeviceToHost));
+  v = f(v);
+  HIP_TRY(hipMemcpy(p, &v, sizeof(v), hipMemcpyHostToDevice));
+  return 0;
+}
+
 // A GEMM on caller operands: upload `in`, poison C with 0xFF (NaN: an element the kernel never
 // writes cannot pass), launch(device operands in order, device C), download C.
 struct HostOperand {

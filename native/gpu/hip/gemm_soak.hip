@@ -281,27 +281,46 @@ __global__ __launch_bounds__(kBlock) void soak_fill(__bf16* __restrict__ X, uint
 // fp32 (C).
 __device__ __forceinline__ long long as_int(__bf16 x) { return static_cast<int>(static_cast<float>(x)); }
 __device__ __forceinline__ long long as_int(float x) { return llrintf(x); }
+// An fp32 C element that is no exact integer (NaN and Inf included) is wrong whatever the sums
+// say: as_int would round an error below 0.5, such as a flipped low mantissa bit, away.
+__device__ __forceinline__ bool inexact(__bf16) { return false; }
+__device__ __forceinline__ bool inexact(float x) { return x != rintf(x) || isinf(x); }
 
 // out[c] += sum over a 64-row slab of X[r][c]  (column sums; atomics over the slabs.  Sum is int
-// or unsigned long long: in two's complement signed sums add correctly)
+// or unsigned long long: in two's complement signed sums add correctly).  flag[c], when given, is
+// set if the column holds an inexact element.
 template <class T, class Sum>
-__global__ __launch_bounds__(kBlock) void soak_colsum(const T* __restrict__ X, int rows, int cols, Sum* __restrict__ out) {
+__global__ __launch_bounds__(kBlock) void soak_colsum(const T* __restrict__ X, int rows, int cols, Sum* __restrict__ out,
+                                                      unsigned* __restrict__ flag = nullptr) {
   const int c = blockIdx.x * kBlock + threadIdx.x;
   if (c >= cols) return;
   const int r0 = blockIdx.y * 64, r1 = min(rows, r0 + 64);
   Sum s = 0;
-  for (int r = r0; r < r1; ++r) s += static_cast<Sum>(as_int(X[static_cast<size_t>(r) * cols + c]));
+  bool odd = false;
+  for (int r = r0; r < r1; ++r) {
+    const T x = X[static_cast<size_t>(r) * cols + c];
+    s += static_cast<Sum>(as_int(x));
+    odd |= inexact(x);
+  }
   atomicAdd(&out[c], s);
+  if (flag && odd) atomicOr(&flag[c], 1u);
 }
 
-// out[r] = sum_k X[r][k] * w[k], or the plain row sum without w  (one block per row)
+// out[r] = sum_k X[r][k] * w[k], or the plain row sum without w  (one block per row).  flag[r],
+// when given, is set if the row holds an inexact element.
 template <class T>
 __global__ __launch_bounds__(kBlock) void soak_rowsum(const T* __restrict__ X, int cols, const int* __restrict__ w,
-                                                      long long* __restrict__ out) {
+                                                      long long* __restrict__ out, unsigned* __restrict__ flag = nullptr) {
   __shared__ long long part[kBlock];
   const size_t base = static_cast<size_t>(blockIdx.x) * cols;
   long long s = 0;
-  for (int k = threadIdx.x; k < cols; k += kBlock) s += as_int(X[base + k]) * (w ? w[k] : 1);
+  bool odd = false;
+  for (int k = threadIdx.x; k < cols; k += kBlock) {
+    const T x = X[base + k];
+    s += as_int(x) * (w ? w[k] : 1);
+    odd |= inexact(x);
+  }
+  if (flag && odd) atomicOr(&flag[blockIdx.x], 1u);
   part[threadIdx.x] = s;
   __syncthreads();
   for (int i = kBlock / 2; i > 0; i >>= 1) {
@@ -348,20 +367,26 @@ bool soak_shape_ok(int m, int n, int k) {
          n <= 32768 && k <= 32768;
 }
 
-}  // namespace
-
-extern "C" {
-
-int bgc_diag_gemm_soak(int device, int m, int n, int k, int launches, uint32_t seed, bgc_soak_result* out) {
-  if (!out || launches <= 0 || !soak_shape_ok(m, n, k)) {
-    g_last_error = "invalid arguments: m, n multiples of 128 and k of 64 (each <= 32768)";
+// bgc_diag_gemm_soak, and bgc_diag_gemm_soak_planted with its test plants added to C after their launch
+int soak_run(int device, int m, int n, int k, int launches, uint32_t seed, const bgc_soak_plant* plants, int n_plants,
+             bgc_soak_result* out) {
+  bool ok = out && launches > 0 && soak_shape_ok(m, n, k) && plant_list_ok(plants, n_plants);
+  for (int j = 0; ok && j < n_plants; ++j) {
+    const bgc_soak_plant& p = plants[j];
+    // only the first and the last launch are verified
+    ok = (p.launch == 0 || p.launch == launches - 1) && p.row >= 0 && p.row < m && p.col >= 0 && p.col < n;
+  }
+  if (!ok) {
+    g_last_error = n_plants ? "invalid arguments: m, n multiples of 128 and k of 64 (each <= 32768); plants inside C, on the first or the last launch"
+                            : "invalid arguments: m, n multiples of 128 and k of 64 (each <= 32768)";
     return 1;
   }
   const SoakKernel kern = soak_kernel(m, n, k);
   std::memset(out, 0, sizeof(*out));
   HIP_TRY(hipSetDevice(device));
   const size_t na = static_cast<size_t>(m) * k, nb = static_cast<size_t>(n) * k, nc = static_cast<size_t>(m) * n;
-  DeviceBuffer a, bt, c, sa, sb, rref, cref, rgot, cgot;
+  DeviceBuffer a, bt, c, sa, sb, rref, cref, rgot, cgot, flags;
+  HIP_TRY(flags.alloc((static_cast<size_t>(m) + n) * 4));  // inexact rows, then columns
   HIP_TRY(a.alloc(na * 2));
   HIP_TRY(bt.alloc(nb * 2));
   HIP_TRY(c.alloc(nc * 4));
@@ -387,17 +412,30 @@ int bgc_diag_gemm_soak(int device, int m, int n, int k, int launches, uint32_t s
       cg(static_cast<size_t>(n));
   HIP_TRY(hipMemcpy(rr.data(), rref.p, rr.size() * 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(cr.data(), cref.p, cr.size() * 8, hipMemcpyDeviceToHost));
+  std::vector<unsigned> fl(static_cast<size_t>(m) + n);
   auto verify = [&](uint64_t* row_bad, uint64_t* col_bad) -> int {
     HIP_TRY(hipMemset(cgot.p, 0, static_cast<size_t>(n) * 8));
+    HIP_TRY(hipMemset(flags.p, 0, fl.size() * 4));
     hipLaunchKernelGGL(soak_rowsum<float>, dim3(m), block, 0, nullptr, c.as<const float>(), n, static_cast<const int*>(nullptr),
-                       rgot.as<long long>());
+                       rgot.as<long long>(), flags.as<unsigned>());
     hipLaunchKernelGGL((soak_colsum<float, unsigned long long>), slabs(m, n), block, 0, nullptr, c.as<const float>(), m, n,
-                       cgot.as<unsigned long long>());
+                       cgot.as<unsigned long long>(), flags.as<unsigned>() + m);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(rg.data(), rgot.p, rg.size() * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(cg.data(), cgot.p, cg.size() * 8, hipMemcpyDeviceToHost));
-    for (int i = 0; i < m; ++i) *row_bad += rg[static_cast<size_t>(i)] != rr[static_cast<size_t>(i)];
-    for (int j = 0; j < n; ++j) *col_bad += cg[static_cast<size_t>(j)] != cr[static_cast<size_t>(j)];
+    HIP_TRY(hipMemcpy(fl.data(), flags.p, fl.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < m; ++i) *row_bad += rg[static_cast<size_t>(i)] != rr[static_cast<size_t>(i)] || fl[static_cast<size_t>(i)];
+    for (int j = 0; j < n; ++j) *col_bad += cg[static_cast<size_t>(j)] != cr[static_cast<size_t>(j)] || fl[static_cast<size_t>(m) + j];
+    return 0;
+  };
+  // test plants of launch `it`, applied once it has finished (timed() waits for it)
+  auto plant = [&](int it) -> int {
+    for (int j = 0; j < n_plants; ++j) {
+      if (plants[j].launch != it) continue;
+      const float delta = plants[j].delta;
+      float* at = c.as<float>() + static_cast<size_t>(plants[j].row) * n + plants[j].col;
+      if (modify_device_value(at, [=](float x) { return x + delta; }) != 0) return 1;
+    }
     return 0;
   };
   Events ev;
@@ -410,6 +448,7 @@ int bgc_diag_gemm_soak(int device, int m, int n, int k, int launches, uint32_t s
     if (timed(ev, &ms, [&] { launch_soak_gemm(kern, a.p, bt.p, c.p, m, n, k); }) != 0) return 1;
     best = std::min(best, ms);
     total += ms;
+    if ((it == 0 || it == launches - 1) && plant(it) != 0) return 1;
     if (it == 0 && verify(&out->row_mismatches, &out->col_mismatches) != 0) return 1;
   }
   if (launches > 1 && verify(&out->row_mismatches, &out->col_mismatches) != 0) return 1;
@@ -423,6 +462,19 @@ int bgc_diag_gemm_soak(int device, int m, int n, int k, int launches, uint32_t s
   out->tflops_best = flop / (best * 1e-3) / 1e12;
   out->tflops_mean = flop * launches / (total * 1e-3) / 1e12;
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bgc_diag_gemm_soak(int device, int m, int n, int k, int launches, uint32_t seed, bgc_soak_result* out) {
+  return soak_run(device, m, n, k, launches, seed, nullptr, 0, out);
+}
+
+int bgc_diag_gemm_soak_planted(int device, int m, int n, int k, int launches, uint32_t seed, const bgc_soak_plant* plants,
+                               int n_plants, bgc_soak_result* out) {
+  return soak_run(device, m, n, k, launches, seed, plants, n_plants, out);
 }
 
 int bgc_diag_gemm_tiled(int device, int m, int n, int k, const uint16_t* a_bf16, const uint16_t* bt_bf16, float* c) {

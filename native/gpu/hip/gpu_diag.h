@@ -15,7 +15,7 @@
 extern "C" {
 #endif
 
-#define BGC_DIAG_ABI_VERSION 11
+#define BGC_DIAG_ABI_VERSION 12
 #define BGC_DIAG_MAX_CU_KEYS 2048
 
 typedef struct {
@@ -24,8 +24,9 @@ typedef struct {
   double write_gbps;       // pattern fill (store-only)
   double read_gbps;        // verify pass (load-only, compare in registers)
   double copy_gbps;        // device-to-device copy kernel (load+store bytes)
-  uint64_t mismatches;     // words that failed the pattern check
-  uint64_t first_bad_word; // index of the first failing word (UINT64_MAX if none)
+  uint64_t mismatches;     // 32-bit words that failed the pattern check, summed over `iters` (the
+                           // counters are not reset between iterations)
+  uint64_t first_bad_word; // index of the first failing 32-bit word (UINT64_MAX if none)
   double elapsed_ms;
 } bgc_hbm_result;
 
@@ -110,8 +111,9 @@ typedef struct {
   double elapsed_ms;        // sum of the launches (device events)
   double tflops_mean;       // over all launches
   double tflops_best;
-  uint64_t row_mismatches;  // C row sums that differ from A (B 1)  (after the first and the last launch)
-  uint64_t col_mismatches;  // C column sums that differ from (1^T A) B
+  uint64_t row_mismatches;  // C rows whose sum differs from A (B 1) or that hold an element that is not
+                            // an exact integer (NaN and Inf included)  (after the first and the last launch)
+  uint64_t col_mismatches;  // C columns alike, against (1^T A) B
   int tile;                 // 256 (256x256 tile, 8 waves) or 128 (128x128, 4 waves)
   int kernel;               // 2: 8-phase ping-pong (K % 128 == 0), 1: double-buffered
 } bgc_soak_result;
@@ -158,6 +160,92 @@ typedef struct {
 // so every cell is checked holding both 0 and 1.  Stops early after `budget_ms`.
 int bgc_diag_hbm_walk(int device, double fraction, uint64_t chunk_bytes, int budget_ms, uint32_t seed,
                       bgc_hbm_walk_result* out);
+// ---------------------------------------------------------------------------------------------
+// Planted variants: FOR TESTS ONLY.  Each runs the same implementation as the entry point it is
+// named after, with a list of deliberately wrong values ("plants") written into the diagnostic's
+// own buffers or accumulators between the phase that produces the data and the phase that checks
+// it, so a test can show that a wrong value reaches the counters.  An empty list is the production
+// behaviour.  Every plant is in bounds: a position outside the buffer, or a wave, lane, round,
+// chain or element index out of range, a negative count or more than BGC_DIAG_MAX_PLANTS is
+// refused with "invalid arguments" before the device is touched (only `wave` has to wait for the
+// device's CU count).  The node agent and the diag worker never load these symbols.
+#define BGC_DIAG_MAX_PLANTS 4096
+#define BGC_PLANT_ALL_WAVES (-1)
+#define BGC_MFMA_CHECK_ROUNDS 8  // tiles per wave of bgc_diag_mfma's check phase
+#define BGC_LOWP_CHECK_ROUNDS 2  // and of each bgc_diag_mfma_lowp variant
+
+typedef struct {
+  uint64_t word32_index;  // 32-bit word of the buffer
+  uint32_t xor_mask;
+} bgc_hbm_plant;
+// One fill, one copy, the plants XORed into the copy in order, one check.  The rates are those of
+// that single cold iteration: no measurement.
+int bgc_diag_hbm_planted(int device, uint64_t bytes, uint32_t seed, const bgc_hbm_plant* plants, int n,
+                         bgc_hbm_result* out);
+
+typedef struct {
+  int pass;                // 0: address pattern, 1: its inverse
+  int chunk;               // allocation, in the order they were made
+  uint64_t word64_offset;  // 64-bit word inside that chunk
+  uint64_t xor_mask;
+} bgc_walk_plant;
+typedef struct {
+  uint64_t base;   // device address
+  uint64_t bytes;
+} bgc_walk_chunk;
+// The walk over `bytes` (rounded down to 2 MiB) in chunks of `chunk_bytes`, without a time
+// budget; each plant is applied after its pass's fill and before its check.  The first
+// min(out->chunks, max_chunks) allocations are returned in `chunks`.  Fails if the device cannot
+// allocate the chunks as `bytes` and `chunk_bytes` imply them.
+int bgc_diag_hbm_walk_planted(int device, uint64_t bytes, uint64_t chunk_bytes, uint32_t seed,
+                              const bgc_walk_plant* plants, int n, bgc_walk_chunk* chunks, int max_chunks,
+                              bgc_hbm_walk_result* out);
+
+typedef struct {
+  uint64_t word64_index;  // 64-bit word of the transfer
+  uint64_t xor_mask;
+} bgc_pcie_plant;
+// One timed iteration; the plants are XORed into the device buffer after the first upload and
+// before the device-to-device and device-to-host copies of the round-trip check.
+int bgc_diag_pcie_planted(int device, uint64_t bytes, uint32_t seed, const bgc_pcie_plant* plants, int n,
+                          bgc_pcie_result* out);
+
+// acc[i] of `lane` += delta in the check phase, before round `round`'s comparison, in wave `wave`
+// (global wave index: block * 4 + wave of the block) or in every wave (BGC_PLANT_ALL_WAVES).  A
+// delta that makes the value NaN counts as a mismatch like any other.
+typedef struct {
+  int wave, round, lane, i;
+  float delta;
+} bgc_mfma_check_plant;
+// acc[chain][i] of `lane` += delta in the throughput phase, after the loop and before the comparison.
+typedef struct {
+  int wave, lane, chain, i;
+  float delta;
+} bgc_mfma_rate_plant;
+int bgc_diag_mfma_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
+                          const bgc_mfma_check_plant* check, int n_check, const bgc_mfma_rate_plant* rate, int n_rate,
+                          bgc_mfma_result* out);
+typedef struct {
+  int variant;  // 0 fp8, 1 fp8 scaled, 2 fp4, 3 fp4 scaled
+  bgc_mfma_check_plant at;
+} bgc_lowp_check_plant;
+typedef struct {
+  int fmt;  // 0 fp8, 1 fp4
+  bgc_mfma_rate_plant at;
+} bgc_lowp_rate_plant;
+int bgc_diag_mfma_lowp_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
+                               const bgc_lowp_check_plant* check, int n_check, const bgc_lowp_rate_plant* rate,
+                               int n_rate, bgc_lowp_result* out);
+
+// C[row][col] += delta after launch `launch` and before its checksums.  Only the first and the
+// last launch are verified: a plant on any other launch is invalid.
+typedef struct {
+  int launch, row, col;
+  float delta;
+} bgc_soak_plant;
+int bgc_diag_gemm_soak_planted(int device, int m, int n, int k, int launches, uint32_t seed,
+                               const bgc_soak_plant* plants, int n_plants, bgc_soak_result* out);
+
 // PCI bus id of a HIP device ("0000:05:00.0", lower-case hex) — the key the node agent and
 // the RCCL probe use to match a HIP device (renumbered inside a container) to amdsmi.
 int bgc_diag_device_bdf(int device, char* buf, size_t len);

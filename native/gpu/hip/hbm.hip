@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kBlock) void hbm_check(const u32x4* __restrict__ bu
   slab_stream<true>(buf, n16, [=, &w](uint64_t i, const u32x4& v) {
     const u32x4 e = pattern16(i, seed);
     const int nb = (v.x != e.x) + (v.y != e.y) + (v.z != e.z) + (v.w != e.w);
-    if (nb) w.add(nb, i * 4);
+    if (nb) w.add(nb, i * 4 + (v.x != e.x ? 0 : v.y != e.y ? 1 : v.z != e.z ? 2 : 3));
   });
   w.report(bad, first_bad);
 }
@@ -172,17 +172,16 @@ uint64_t mix64(uint64_t x) {
   return x;
 }
 
-}  // namespace
-
-extern "C" {
-
-int bgc_diag_hbm(int device, uint64_t bytes, int iters, uint32_t seed, bgc_hbm_result* out) {
-  if (!out || iters <= 0 || bytes < (1u << 20)) {
+// bgc_diag_hbm, and bgc_diag_hbm_planted with its test plants XORed into the copy before each check
+int hbm_run(int device, uint64_t bytes, int iters, uint32_t seed, const bgc_hbm_plant* plants, int n, bgc_hbm_result* out) {
+  bool ok = out && iters > 0 && bytes >= (1u << 20) && plant_list_ok(plants, n);
+  bytes &= ~static_cast<uint64_t>(15);
+  for (int j = 0; ok && j < n; ++j) ok = plants[j].word32_index < bytes / 4;
+  if (!ok) {
     g_last_error = "invalid arguments";
     return 1;
   }
   std::memset(out, 0, sizeof(*out));
-  bytes &= ~static_cast<uint64_t>(15);
   const uint64_t n16 = bytes / 16;
   HIP_TRY(hipSetDevice(device));
   DeviceBuffer a, b, counters;
@@ -208,7 +207,12 @@ int bgc_diag_hbm(int device, uint64_t bytes, int iters, uint32_t seed, bgc_hbm_r
   fill();  // warm-up (also first-touch of the pages)
   HIP_TRY(hipGetLastError());
   for (int it = 0; it < iters; ++it) {
-    if (phase(fill, &best_fill) != 0 || phase(copy, &best_copy) != 0 || phase(check, &best_check) != 0) return 1;
+    if (phase(fill, &best_fill) != 0 || phase(copy, &best_copy) != 0) return 1;
+    for (int j = 0; j < n; ++j) {
+      const uint32_t mask = plants[j].xor_mask;
+      if (modify_device_value(b.as<uint32_t>() + plants[j].word32_index, [=](uint32_t w) { return w ^ mask; }) != 0) return 1;
+    }
+    if (phase(check, &best_check) != 0) return 1;
   }
   unsigned long long res[2];
   HIP_TRY(hipMemcpy(res, bad, sizeof(res), hipMemcpyDeviceToHost));
@@ -223,13 +227,15 @@ int bgc_diag_hbm(int device, uint64_t bytes, int iters, uint32_t seed, bgc_hbm_r
   return 0;
 }
 
-int bgc_diag_hbm_walk(int device, double fraction, uint64_t chunk_bytes, int budget_ms, uint32_t seed,
-                      bgc_hbm_walk_result* out) {
-  constexpr uint64_t kMinChunk = 64ULL << 20;
-  if (!out || !(fraction > 0.0 && fraction <= 0.99) || chunk_bytes < kMinChunk || budget_ms <= 0) {
-    g_last_error = "invalid arguments: 0 < fraction <= 0.99, chunk_bytes >= 64 MiB, budget_ms > 0";
-    return 1;
-  }
+constexpr uint64_t kMinChunk = 64ULL << 20;
+constexpr uint64_t kWalkAlign = 2ULL << 20;
+
+// The walk over `target_bytes`, or over `fraction` of the free VRAM when that is 0 (arguments
+// checked by the callers).  Test plants are XORed in after their pass's fill; with any, the
+// allocations must come out as `target_bytes` and `chunk_bytes` imply, since the plants were
+// checked against that layout.
+int walk_run(int device, double fraction, uint64_t target_bytes, uint64_t chunk_bytes, int budget_ms, uint32_t seed,
+             const bgc_walk_plant* plants, int n, bgc_walk_chunk* chunks_out, int max_chunks, bgc_hbm_walk_result* out) {
   std::memset(out, 0, sizeof(*out));
   const auto t0 = std::chrono::steady_clock::now();
   auto elapsed_ms = [&] {
@@ -242,8 +248,8 @@ int bgc_diag_hbm_walk(int device, double fraction, uint64_t chunk_bytes, int bud
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   out->free_bytes = free_b;
   out->total_bytes = total_b;
-  const uint64_t align = 2ULL << 20;
-  const uint64_t target = static_cast<uint64_t>(fraction * static_cast<double>(free_b)) & ~(align - 1);
+  const uint64_t align = kWalkAlign;
+  const uint64_t target = (target_bytes ? target_bytes : static_cast<uint64_t>(fraction * static_cast<double>(free_b))) & ~(align - 1);
   out->target_bytes = target;
   Chunks chunks;
   uint64_t got = 0, cb = chunk_bytes & ~(align - 1);
@@ -265,6 +271,13 @@ int bgc_diag_hbm_walk(int device, double fraction, uint64_t chunk_bytes, int bud
   }
   out->chunks = static_cast<int>(chunks.v.size());
   out->alloc_ms = elapsed_ms();
+  for (int c = 0; c < out->chunks && c < max_chunks; ++c) {
+    chunks_out[c] = {reinterpret_cast<uint64_t>(chunks.v[static_cast<size_t>(c)].first), chunks.v[static_cast<size_t>(c)].second};
+  }
+  if (n > 0 && (got != target || cb != (chunk_bytes & ~(align - 1)))) {
+    g_last_error = "hbm walk: the chunks could not be allocated as the plants assume";
+    return 1;
+  }
   auto* bad = counters.as<unsigned long long>();
   const dim3 grid(cu_count(device) * 8), block(kBlock);
   Events ev;
@@ -287,6 +300,12 @@ int bgc_diag_hbm_walk(int device, double fraction, uint64_t chunk_bytes, int bud
       return 1;
     }
     fill_ms += ms;
+    for (int j = 0; j < n; ++j) {
+      if (plants[j].pass != pass) continue;
+      const uint64_t mask = plants[j].xor_mask;
+      auto* word = static_cast<uint64_t*>(chunks.v[static_cast<size_t>(plants[j].chunk)].first) + plants[j].word64_offset;
+      if (modify_device_value(word, [=](uint64_t w) { return w ^ mask; }) != 0) return 1;
+    }
     if (timed(ev, &ms, [&] {
           for (const auto& c : chunks.v) {
             hipLaunchKernelGGL(walk_check, grid, block, 0, nullptr, static_cast<const u32x4*>(c.first), c.second / 16, key,
@@ -315,14 +334,17 @@ int bgc_diag_hbm_walk(int device, double fraction, uint64_t chunk_bytes, int bud
   return 0;
 }
 
-int bgc_diag_pcie(int device, uint64_t bytes, int iters, uint32_t seed, bgc_pcie_result* out) {
-  if (!out || iters <= 0 || bytes < (1u << 20) || bytes > (uint64_t{16} << 30)) {
+// bgc_diag_pcie, and bgc_diag_pcie_planted with its test plants XORed into the uploaded buffer
+int pcie_run(int device, uint64_t bytes, int iters, uint32_t seed, const bgc_pcie_plant* plants, int n, bgc_pcie_result* out) {
+  bool ok = out && iters > 0 && bytes >= (1u << 20) && bytes <= (uint64_t{16} << 30) && plant_list_ok(plants, n);
+  bytes &= ~static_cast<uint64_t>(7);
+  const uint64_t words = bytes / 8;
+  for (int j = 0; ok && j < n; ++j) ok = plants[j].word64_index < words;
+  if (!ok) {
     g_last_error = "invalid arguments";
     return 1;
   }
   std::memset(out, 0, sizeof(*out));
-  bytes &= ~static_cast<uint64_t>(7);
-  const uint64_t words = bytes / 8;
   HIP_TRY(hipSetDevice(device));
   HostBuffer src, dst, src2;
   DeviceBuffer d1, d2;
@@ -342,6 +364,11 @@ int bgc_diag_pcie(int device, uint64_t bytes, int iters, uint32_t seed, bgc_pcie
   HIP_TRY(ev2.create());
   // warm-up both directions (page tables, DMA engine clocks)
   HIP_TRY(hipMemcpyAsync(d1.p, src.p, bytes, hipMemcpyHostToDevice, st.a));
+  if (n > 0) HIP_TRY(hipStreamSynchronize(st.a));  // the upload has landed; the copies below are issued after the plants
+  for (int j = 0; j < n; ++j) {
+    const uint64_t mask = plants[j].xor_mask;
+    if (modify_device_value(d1.as<uint64_t>() + plants[j].word64_index, [=](uint64_t w) { return w ^ mask; }) != 0) return 1;
+  }
   HIP_TRY(hipMemcpyAsync(d2.p, d1.p, bytes, hipMemcpyDeviceToDevice, st.a));
   HIP_TRY(hipMemcpyAsync(dst.p, d2.p, bytes, hipMemcpyDeviceToHost, st.a));
   HIP_TRY(hipStreamSynchronize(st.a));
@@ -383,6 +410,53 @@ int bgc_diag_pcie(int device, uint64_t bytes, int iters, uint32_t seed, bgc_pcie
   out->mismatches = bad;
   out->elapsed_ms = total;
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bgc_diag_hbm(int device, uint64_t bytes, int iters, uint32_t seed, bgc_hbm_result* out) {
+  return hbm_run(device, bytes, iters, seed, nullptr, 0, out);
+}
+
+int bgc_diag_hbm_planted(int device, uint64_t bytes, uint32_t seed, const bgc_hbm_plant* plants, int n, bgc_hbm_result* out) {
+  return hbm_run(device, bytes, 1, seed, plants, n, out);
+}
+
+int bgc_diag_hbm_walk(int device, double fraction, uint64_t chunk_bytes, int budget_ms, uint32_t seed,
+                      bgc_hbm_walk_result* out) {
+  if (!out || !(fraction > 0.0 && fraction <= 0.99) || chunk_bytes < kMinChunk || budget_ms <= 0) {
+    g_last_error = "invalid arguments: 0 < fraction <= 0.99, chunk_bytes >= 64 MiB, budget_ms > 0";
+    return 1;
+  }
+  return walk_run(device, fraction, 0, chunk_bytes, budget_ms, seed, nullptr, 0, nullptr, 0, out);
+}
+
+int bgc_diag_hbm_walk_planted(int device, uint64_t bytes, uint64_t chunk_bytes, uint32_t seed, const bgc_walk_plant* plants,
+                              int n, bgc_walk_chunk* chunks, int max_chunks, bgc_hbm_walk_result* out) {
+  const uint64_t target = bytes & ~(kWalkAlign - 1), cb = chunk_bytes & ~(kWalkAlign - 1);
+  bool ok = out && target > 0 && target <= (1ULL << 40) && chunk_bytes >= kMinChunk && plant_list_ok(plants, n) &&
+            max_chunks >= 0 && (max_chunks == 0 || chunks);
+  const uint64_t n_chunks = ok ? (target + cb - 1) / cb : 0;  // as the allocation loop splits the target
+  for (int j = 0; ok && j < n; ++j) {
+    const bgc_walk_plant& p = plants[j];
+    ok = (p.pass == 0 || p.pass == 1) && p.chunk >= 0 && static_cast<uint64_t>(p.chunk) < n_chunks &&
+         p.word64_offset < std::min(cb, target - static_cast<uint64_t>(p.chunk) * cb) / 8;
+  }
+  if (!ok) {
+    g_last_error = "invalid arguments: bytes >= 2 MiB, chunk_bytes >= 64 MiB, plants inside their chunk, pass 0 or 1";
+    return 1;
+  }
+  return walk_run(device, 0.0, target, chunk_bytes, INT32_MAX, seed, plants, n, chunks, max_chunks, out);
+}
+
+int bgc_diag_pcie(int device, uint64_t bytes, int iters, uint32_t seed, bgc_pcie_result* out) {
+  return pcie_run(device, bytes, iters, seed, nullptr, 0, out);
+}
+
+int bgc_diag_pcie_planted(int device, uint64_t bytes, uint32_t seed, const bgc_pcie_plant* plants, int n, bgc_pcie_result* out) {
+  return pcie_run(device, bytes, 1, seed, plants, n, out);
 }
 
 }  // extern "C"

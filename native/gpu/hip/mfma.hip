@@ -140,8 +140,54 @@ struct CheckWave {
   }
 };
 
+// Test plants (gpu_diag.h, "planted variants").  The check and throughput kernels end in a pack
+// `Plants... plants`: empty in the production instantiations, which so take no further argument and
+// call the empty plant() overloads (they compile to what they would be without), and one plant list
+// in the instantiations behind the *_planted entry points.  Everything else, the comparison, the
+// wave reduction and the report, is the same source for both.
+struct CheckPlants {
+  const bgc_mfma_check_plant* p;
+  int n;
+};
+struct RatePlants {
+  const bgc_mfma_rate_plant* p = nullptr;
+  int n = 0;
+};
+
+__device__ __forceinline__ void add_at(f32x4& acc, int i, float delta) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (e == i) acc[e] += delta;
+  }
+}
+
+// check phase: before round `round`'s comparison
+__device__ __forceinline__ void plant(f32x4&, uint32_t /*wave*/, int /*round*/, int /*lane*/) {}
+__device__ __forceinline__ void plant(f32x4& acc, uint32_t wave, int round, int lane, CheckPlants pl) {
+  for (int j = 0; j < pl.n; ++j) {
+    const bgc_mfma_check_plant p = pl.p[j];
+    if ((p.wave == BGC_PLANT_ALL_WAVES || static_cast<uint32_t>(p.wave) == wave) && p.round == round && p.lane == lane) {
+      add_at(acc, p.i, p.delta);
+    }
+  }
+}
+
+// throughput phase: after the loop, before the comparison
+__device__ __forceinline__ void plant(f32x4 (&)[4], uint32_t /*wave*/, int /*lane*/) {}
+__device__ __forceinline__ void plant(f32x4 (&acc)[4], uint32_t wave, int lane, RatePlants pl) {
+  for (int j = 0; j < pl.n; ++j) {
+    const bgc_mfma_rate_plant p = pl.p[j];
+    if (static_cast<uint32_t>(p.wave) != wave || p.lane != lane) continue;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (c == p.chain) add_at(acc[c], p.i, p.delta);
+    }
+  }
+}
+
+template <class... Plants>
 __global__ __launch_bounds__(kBlock) void mfma_check(uint32_t seed, int rounds, unsigned* __restrict__ cu_tiles,
-                                                     unsigned* __restrict__ cu_bad) {
+                                                     unsigned* __restrict__ cu_bad, Plants... plants) {
   const CheckWave w;
   const int rc = w.lane & 15, g = w.lane >> 4;
   unsigned bad = 0;
@@ -149,7 +195,8 @@ __global__ __launch_bounds__(kBlock) void mfma_check(uint32_t seed, int rounds, 
     const uint32_t tile = w.tile(rounds, r);
     const bf16x8 a = Bf16Tile::pack(seed, tile, rc, g, 0xA);
     const bf16x8 b = Bf16Tile::pack(seed, tile, rc, g, 0xB);
-    const f32x4 acc = Bf16Tile::mfma(a, b, f32x4{0.f, 0.f, 0.f, 0.f});
+    f32x4 acc = Bf16Tile::mfma(a, b, f32x4{0.f, 0.f, 0.f, 0.f});
+    plant(acc, w.wave, r, w.lane, plants...);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int orow = 4 * g + i;
@@ -162,10 +209,10 @@ __global__ __launch_bounds__(kBlock) void mfma_check(uint32_t seed, int rounds, 
   w.report(rounds, bad, cu_tiles, cu_bad);
 }
 
-template <int kFmt>
+template <int kFmt, class... Plants>
 __global__ __launch_bounds__(kBlock) void mfma_lowp_check(uint32_t seed, int rounds, int scaled,
                                                           unsigned* __restrict__ cu_tiles,
-                                                          unsigned* __restrict__ cu_bad) {
+                                                          unsigned* __restrict__ cu_bad, Plants... plants) {
   const CheckWave w;
   const int rc = w.lane & 15, g = w.lane >> 4;
   unsigned bad = 0;
@@ -175,6 +222,7 @@ __global__ __launch_bounds__(kBlock) void mfma_lowp_check(uint32_t seed, int rou
     const i32x8 b = MxTile<kFmt>::pack(seed, tile, rc, g, 0xB);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     acc = lowp_mfma<kFmt>(a, b, acc, lowp_exp(seed, tile, rc, g, 0xA, scaled), lowp_exp(seed, tile, rc, g, 0xB, scaled));
+    plant(acc, w.wave, r, w.lane, plants...);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int orow = 4 * g + i;
@@ -202,10 +250,10 @@ __global__ __launch_bounds__(kBlock) void mfma_lowp_check(uint32_t seed, int rou
 // each wave also times itself on the 100 MHz constant clock and adds its duration to its XCC's
 // bin, so a slow (throttled / degraded) XCC shows up as an imbalance even when the whole-chip
 // rate still clears its floor.
-template <class Tile, bool kTimed>
+template <class Tile, bool kTimed, class... Plants>
 __global__ __launch_bounds__(kBlock) void mfma_throughput(uint32_t seed, int iters, unsigned* __restrict__ fails,
                                                           unsigned long long* __restrict__ xcc_ticks,
-                                                          unsigned* __restrict__ xcc_waves) {
+                                                          unsigned* __restrict__ xcc_waves, Plants... plants) {
   uint64_t t_start = 0;
   if constexpr (kTimed) t_start = wall_clock64();
   const int lane = threadIdx.x & 63;
@@ -221,6 +269,7 @@ __global__ __launch_bounds__(kBlock) void mfma_throughput(uint32_t seed, int ite
 #pragma unroll
     for (int c = 0; c < 4; ++c) acc[c] = Tile::mfma(a, b, acc[c]);
   }
+  plant(acc, tile, lane, plants...);
   unsigned bad = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -322,35 +371,72 @@ void with_mx_fmt(int fmt, F&& f) {
   }
 }
 
+// the production instantiation, or with test plants the planted one
+template <class Tile, bool kTimed>
+void launch_rate(int blocks, uint32_t seed, int iters, unsigned* fails, unsigned long long* xt, unsigned* xw, RatePlants plants) {
+  if (plants.n == 0) {
+    hipLaunchKernelGGL((mfma_throughput<Tile, kTimed>), dim3(blocks), dim3(kBlock), 0, nullptr, seed, iters, fails, xt, xw);
+  } else {
+    hipLaunchKernelGGL((mfma_throughput<Tile, kTimed, RatePlants>), dim3(blocks), dim3(kBlock), 0, nullptr, seed, iters, fails,
+                       xt, xw, plants);
+  }
+}
+
 // one throughput launch of a burn dtype: bf16 (timed per XCC into xt / xw) or MX fp8 / fp4
 void launch_throughput(int dtype, int blocks, uint32_t seed, int iters, unsigned* fails, unsigned long long* xt = nullptr,
-                       unsigned* xw = nullptr) {
+                       unsigned* xw = nullptr, RatePlants plants = {}) {
   if (dtype == BGC_BURN_BF16) {
-    hipLaunchKernelGGL((mfma_throughput<Bf16Tile, true>), dim3(blocks), dim3(kBlock), 0, nullptr, seed, iters, fails, xt, xw);
+    launch_rate<Bf16Tile, true>(blocks, seed, iters, fails, xt, xw, plants);
   } else {
-    with_mx_fmt(dtype == BGC_BURN_FP8 ? 0 : 4, [&](auto fmt) {
-      hipLaunchKernelGGL((mfma_throughput<MxTile<decltype(fmt)::value>, false>), dim3(blocks), dim3(kBlock), 0, nullptr, seed,
-                         iters, fails, xt, xw);
-    });
+    with_mx_fmt(dtype == BGC_BURN_FP8 ? 0 : 4,
+                [&](auto fmt) { launch_rate<MxTile<decltype(fmt)::value>, false>(blocks, seed, iters, fails, xt, xw, plants); });
   }
 }
 
 // waves of `waves_per_cu` per CU as kBlock-thread blocks
 int wave_blocks(int device, int waves_per_cu) { return std::max(1, cu_count(device) * waves_per_cu / (kBlock / 64)); }
 
-}  // namespace
+// Host checks of test plants, all but `wave` before the device is touched.
+bool check_plant_ok(const bgc_mfma_check_plant& p, int rounds) {
+  return p.wave >= BGC_PLANT_ALL_WAVES && p.round >= 0 && p.round < rounds && p.lane >= 0 && p.lane < 64 && p.i >= 0 && p.i < 4;
+}
+bool rate_plant_ok(const bgc_mfma_rate_plant& p) {
+  return p.wave >= 0 && p.lane >= 0 && p.lane < 64 && p.chain >= 0 && p.chain < 4 && p.i >= 0 && p.i < 4;
+}
 
-extern "C" {
+// plants in device memory; none allocates nothing
+template <class P>
+int upload_plants(DeviceBuffer& d, const std::vector<P>& plants) {
+  if (plants.empty()) return 0;
+  HIP_TRY(d.alloc(plants.size() * sizeof(P)));
+  HIP_TRY(hipMemcpy(d.p, plants.data(), plants.size() * sizeof(P), hipMemcpyHostToDevice));
+  return 0;
+}
 
-int bgc_diag_mfma(int device, int waves_per_cu, int throughput_iters, uint32_t seed, bgc_mfma_result* out) {
-  if (!out || waves_per_cu <= 0 || throughput_iters <= 0 || throughput_iters > (1 << 18)) {
+int mfma_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_mfma_check_plant* check, int n_check,
+             const bgc_mfma_rate_plant* rate, int n_rate, bgc_mfma_result* out) {
+  const int rounds = BGC_MFMA_CHECK_ROUNDS;
+  bool ok = out && waves_per_cu > 0 && throughput_iters > 0 && throughput_iters <= (1 << 18) && plant_list_ok(check, n_check) &&
+            plant_list_ok(rate, n_rate);
+  for (int j = 0; ok && j < n_check; ++j) ok = check_plant_ok(check[j], rounds);
+  for (int j = 0; ok && j < n_rate; ++j) ok = rate_plant_ok(rate[j]);
+  if (!ok) {
     g_last_error = "invalid arguments";
     return 1;
   }
   std::memset(out, 0, sizeof(*out));
   HIP_TRY(hipSetDevice(device));
   const int blocks = wave_blocks(device, waves_per_cu);
-  const int rounds = 8;
+  const std::vector<bgc_mfma_check_plant> h_check(check, check + n_check);
+  const std::vector<bgc_mfma_rate_plant> h_rate(rate, rate + n_rate);
+  for (const auto& p : h_check) ok = ok && p.wave < blocks * (kBlock / 64);
+  for (const auto& p : h_rate) ok = ok && p.wave < blocks * (kBlock / 64);
+  if (!ok) {
+    g_last_error = "invalid arguments: plant in a wave beyond the launch";
+    return 1;
+  }
+  DeviceBuffer d_check, d_rate;
+  if (upload_plants(d_check, h_check) != 0 || upload_plants(d_rate, h_rate) != 0) return 1;
   DeviceBuffer tiles, bad, fails, xticks, xwaves;
   HIP_TRY(tiles.alloc(BGC_DIAG_MAX_CU_KEYS * sizeof(unsigned), true));
   HIP_TRY(bad.alloc(BGC_DIAG_MAX_CU_KEYS * sizeof(unsigned), true));
@@ -361,8 +447,13 @@ int bgc_diag_mfma(int device, int waves_per_cu, int throughput_iters, uint32_t s
   HIP_TRY(ev.create());
   float ms_check = 0.f, ms_tp = 0.f;
   if (timed(ev, &ms_check, [&] {
-        hipLaunchKernelGGL(mfma_check, dim3(blocks), dim3(kBlock), 0, nullptr, seed, rounds, tiles.as<unsigned>(),
-                           bad.as<unsigned>());
+        if (n_check == 0) {
+          hipLaunchKernelGGL(mfma_check<>, dim3(blocks), dim3(kBlock), 0, nullptr, seed, rounds, tiles.as<unsigned>(),
+                             bad.as<unsigned>());
+        } else {
+          hipLaunchKernelGGL(mfma_check<CheckPlants>, dim3(blocks), dim3(kBlock), 0, nullptr, seed, rounds, tiles.as<unsigned>(),
+                             bad.as<unsigned>(), CheckPlants{d_check.as<const bgc_mfma_check_plant>(), n_check});
+        }
       }) != 0) {
     return 1;
   }
@@ -373,7 +464,8 @@ int bgc_diag_mfma(int device, int waves_per_cu, int throughput_iters, uint32_t s
   HIP_TRY(hipMemset(fails.p, 0, sizeof(unsigned)));
   HIP_TRY(hipMemset(xticks.p, 0, 8 * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(xwaves.p, 0, 8 * sizeof(unsigned)));
-  if (timed(ev, &ms_tp, [&] { launch_throughput(BGC_BURN_BF16, blocks, seed, throughput_iters, fails.as<unsigned>(), xt, xw); }) != 0) {
+  const RatePlants rate_plants{d_rate.as<const bgc_mfma_rate_plant>(), n_rate};
+  if (timed(ev, &ms_tp, [&] { launch_throughput(BGC_BURN_BF16, blocks, seed, throughput_iters, fails.as<unsigned>(), xt, xw, rate_plants); }) != 0) {
     return 1;
   }
   std::vector<unsigned> h_tiles(BGC_DIAG_MAX_CU_KEYS), h_bad(BGC_DIAG_MAX_CU_KEYS);
@@ -419,15 +511,52 @@ int bgc_diag_mfma(int device, int waves_per_cu, int throughput_iters, uint32_t s
   return 0;
 }
 
-int bgc_diag_mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint32_t seed, bgc_lowp_result* out) {
-  if (!out || waves_per_cu <= 0 || waves_per_cu > 64 || throughput_iters <= 0 || throughput_iters > (1 << 16)) {
+int lowp_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_lowp_check_plant* check, int n_check,
+             const bgc_lowp_rate_plant* rate, int n_rate, bgc_lowp_result* out) {
+  const int rounds = BGC_LOWP_CHECK_ROUNDS;
+  bool ok = out && waves_per_cu > 0 && waves_per_cu <= 64 && throughput_iters > 0 && throughput_iters <= (1 << 16) &&
+            plant_list_ok(check, n_check) && plant_list_ok(rate, n_rate);
+  for (int j = 0; ok && j < n_check; ++j) ok = check[j].variant >= 0 && check[j].variant < 4 && check_plant_ok(check[j].at, rounds);
+  for (int j = 0; ok && j < n_rate; ++j) ok = (rate[j].fmt == 0 || rate[j].fmt == 1) && rate_plant_ok(rate[j].at);
+  if (!ok) {
     g_last_error = "invalid arguments";
     return 1;
   }
   std::memset(out, 0, sizeof(*out));
   HIP_TRY(hipSetDevice(device));
   const int blocks = wave_blocks(device, waves_per_cu);
-  const int rounds = 2;
+  // test plants, sorted by the launch they belong to: check variant [fmt][scaled], rate format
+  std::vector<bgc_mfma_check_plant> h_check[4];
+  std::vector<bgc_mfma_rate_plant> h_rate[2];
+  for (int j = 0; j < n_check; ++j) {
+    ok = ok && check[j].at.wave < blocks * (kBlock / 64);
+    h_check[check[j].variant].push_back(check[j].at);
+  }
+  for (int j = 0; j < n_rate; ++j) {
+    ok = ok && rate[j].at.wave < blocks * (kBlock / 64);
+    h_rate[rate[j].fmt].push_back(rate[j].at);
+  }
+  if (!ok) {
+    g_last_error = "invalid arguments: plant in a wave beyond the launch";
+    return 1;
+  }
+  DeviceBuffer d_check[4], d_rate[2];
+  for (int v = 0; v < 4; ++v) {
+    if (upload_plants(d_check[v], h_check[v]) != 0) return 1;
+  }
+  for (int i = 0; i < 2; ++i) {
+    if (upload_plants(d_rate[i], h_rate[i]) != 0) return 1;
+  }
+  auto launch_check = [&](auto fmt, int sc, unsigned* tiles_v, unsigned* bad_v) {
+    constexpr int kFmt = decltype(fmt)::value;
+    const int v = (kFmt == 0 ? 0 : 2) + sc;
+    if (h_check[v].empty()) {
+      hipLaunchKernelGGL(mfma_lowp_check<kFmt>, dim3(blocks), dim3(kBlock), 0, nullptr, seed, rounds, sc, tiles_v, bad_v);
+    } else {
+      hipLaunchKernelGGL((mfma_lowp_check<kFmt, CheckPlants>), dim3(blocks), dim3(kBlock), 0, nullptr, seed, rounds, sc, tiles_v, bad_v,
+                         CheckPlants{d_check[v].as<const bgc_mfma_check_plant>(), static_cast<int>(h_check[v].size())});
+    }
+  };
   // bins: [fmt][scaled] tiles and mismatches per CU key
   DeviceBuffer tiles, bad, fails;
   const size_t bins = 4 * static_cast<size_t>(BGC_DIAG_MAX_CU_KEYS);
@@ -443,8 +572,8 @@ int bgc_diag_mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint3
   if (timed(ev, &total, [&] {
         for (int sc = 0; sc < 2; ++sc) {
           const size_t o8 = static_cast<size_t>(sc) * BGC_DIAG_MAX_CU_KEYS, o4 = (2 + static_cast<size_t>(sc)) * BGC_DIAG_MAX_CU_KEYS;
-          hipLaunchKernelGGL(mfma_lowp_check<0>, dim3(blocks), dim3(kBlock), 0, nullptr, seed, rounds, sc, t + o8, b + o8);
-          hipLaunchKernelGGL(mfma_lowp_check<4>, dim3(blocks), dim3(kBlock), 0, nullptr, seed, rounds, sc, t + o4, b + o4);
+          launch_check(std::integral_constant<int, 0>{}, sc, t + o8, b + o8);
+          launch_check(std::integral_constant<int, 4>{}, sc, t + o4, b + o4);
         }
       }) != 0) {
     return 1;
@@ -454,7 +583,10 @@ int bgc_diag_mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint3
   HIP_TRY(hipMemset(f, 0, 2 * sizeof(unsigned)));
   float ms_fmt[2] = {0.f, 0.f};
   for (int i = 0; i < 2; ++i) {
-    if (timed(ev, &ms_fmt[i], [&] { launch_throughput(i == 0 ? BGC_BURN_FP8 : BGC_BURN_FP4, blocks, seed, throughput_iters, f + i); }) != 0) {
+    const RatePlants rate_plants{d_rate[i].as<const bgc_mfma_rate_plant>(), static_cast<int>(h_rate[i].size())};
+    if (timed(ev, &ms_fmt[i], [&] {
+          launch_throughput(i == 0 ? BGC_BURN_FP8 : BGC_BURN_FP4, blocks, seed, throughput_iters, f + i, nullptr, nullptr, rate_plants);
+        }) != 0) {
       return 1;
     }
     total += ms_fmt[i];
@@ -489,6 +621,28 @@ int bgc_diag_mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint3
   out->throughput_ok = h_f[0] == 0 && h_f[1] == 0;
   out->elapsed_ms = total;
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bgc_diag_mfma(int device, int waves_per_cu, int throughput_iters, uint32_t seed, bgc_mfma_result* out) {
+  return mfma_run(device, waves_per_cu, throughput_iters, seed, nullptr, 0, nullptr, 0, out);
+}
+
+int bgc_diag_mfma_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_mfma_check_plant* check,
+                          int n_check, const bgc_mfma_rate_plant* rate, int n_rate, bgc_mfma_result* out) {
+  return mfma_run(device, waves_per_cu, throughput_iters, seed, check, n_check, rate, n_rate, out);
+}
+
+int bgc_diag_mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint32_t seed, bgc_lowp_result* out) {
+  return lowp_run(device, waves_per_cu, throughput_iters, seed, nullptr, 0, nullptr, 0, out);
+}
+
+int bgc_diag_mfma_lowp_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_lowp_check_plant* check,
+                               int n_check, const bgc_lowp_rate_plant* rate, int n_rate, bgc_lowp_result* out) {
+  return lowp_run(device, waves_per_cu, throughput_iters, seed, check, n_check, rate, n_rate, out);
 }
 
 int bgc_diag_burn(int device, int duration_ms, int waves_per_cu, uint32_t seed, bgc_burn_result* out) {

@@ -286,6 +286,81 @@ void register_gpu(py::module_& m) {
     return v.dump();
   }, py::arg("device"), py::arg("m") = 8192, py::arg("n") = 8192, py::arg("k") = 8192, py::arg("launches") = 10,
      py::arg("seed") = 0x5eed);
+  // Planted variants (gpu_diag.h): for tests only.  Plants are lists of tuples in the order of the
+  // C structs' fields; the library checks them ("invalid arguments") before it touches the GPU.
+  using u64 = unsigned long long;
+  m.def("diag_hbm_planted", [](int device, u64 bytes, unsigned seed, const std::vector<std::tuple<u64, unsigned>>& plants) {
+    std::vector<bgc_hbm_plant> p;
+    for (const auto& [word, mask] : plants) p.push_back({word, mask});
+    Value v;
+    {
+      py::gil_scoped_release nogil;
+      v = bgc::gpu::Diag::instance().hbm_planted(device, bytes, seed, p);
+    }
+    return v.dump();
+  }, py::arg("device"), py::arg("bytes"), py::arg("seed"), py::arg("plants"));
+  m.def("diag_hbm_walk_planted", [](int device, u64 bytes, u64 chunk_bytes, unsigned seed,
+                                    const std::vector<std::tuple<int, int, u64, u64>>& plants) {
+    std::vector<bgc_walk_plant> p;
+    for (const auto& [pass, chunk, offset, mask] : plants) p.push_back({pass, chunk, offset, mask});
+    Value v;
+    {
+      py::gil_scoped_release nogil;
+      v = bgc::gpu::Diag::instance().hbm_walk_planted(device, bytes, chunk_bytes, seed, p);
+    }
+    return v.dump();
+  }, py::arg("device"), py::arg("bytes"), py::arg("chunk_bytes"), py::arg("seed"), py::arg("plants"));
+  m.def("diag_pcie_planted", [](int device, u64 bytes, unsigned seed, const std::vector<std::tuple<u64, u64>>& plants) {
+    std::vector<bgc_pcie_plant> p;
+    for (const auto& [word, mask] : plants) p.push_back({word, mask});
+    Value v;
+    {
+      py::gil_scoped_release nogil;
+      v = bgc::gpu::Diag::instance().pcie_planted(device, bytes, seed, p);
+    }
+    return v.dump();
+  }, py::arg("device"), py::arg("bytes"), py::arg("seed"), py::arg("plants"));
+  using AccPlant = std::tuple<int, int, int, int, float>;       // check: wave, round, lane, i, delta; rate: wave, lane, chain, i, delta
+  using LowpPlant = std::tuple<int, int, int, int, int, float>;  // the variant (check) or format (rate) in front
+  m.def("diag_mfma_planted", [](int device, int waves_per_cu, int iters, unsigned seed, const std::vector<AccPlant>& check,
+                                const std::vector<AccPlant>& rate) {
+    std::vector<bgc_mfma_check_plant> c;
+    std::vector<bgc_mfma_rate_plant> r;
+    for (const auto& [wave, round, lane, i, delta] : check) c.push_back({wave, round, lane, i, delta});
+    for (const auto& [wave, lane, chain, i, delta] : rate) r.push_back({wave, lane, chain, i, delta});
+    Value v;
+    {
+      py::gil_scoped_release nogil;
+      v = bgc::gpu::Diag::instance().mfma_planted(device, waves_per_cu, iters, seed, c, r);
+    }
+    return v.dump();
+  }, py::arg("device"), py::arg("waves_per_cu"), py::arg("iters"), py::arg("seed"), py::arg("check_plants"),
+     py::arg("rate_plants"));
+  m.def("diag_mfma_lowp_planted", [](int device, int waves_per_cu, int iters, unsigned seed, const std::vector<LowpPlant>& check,
+                                     const std::vector<LowpPlant>& rate) {
+    std::vector<bgc_lowp_check_plant> c;
+    std::vector<bgc_lowp_rate_plant> r;
+    for (const auto& [variant, wave, round, lane, i, delta] : check) c.push_back({variant, {wave, round, lane, i, delta}});
+    for (const auto& [fmt, wave, lane, chain, i, delta] : rate) r.push_back({fmt, {wave, lane, chain, i, delta}});
+    Value v;
+    {
+      py::gil_scoped_release nogil;
+      v = bgc::gpu::Diag::instance().mfma_lowp_planted(device, waves_per_cu, iters, seed, c, r);
+    }
+    return v.dump();
+  }, py::arg("device"), py::arg("waves_per_cu"), py::arg("iters"), py::arg("seed"), py::arg("check_plants"),
+     py::arg("rate_plants"));
+  m.def("diag_gemm_soak_planted", [](int device, int mm, int nn, int kk, int launches, unsigned seed,
+                                     const std::vector<std::tuple<int, int, int, float>>& plants) {
+    std::vector<bgc_soak_plant> p;
+    for (const auto& [launch, row, col, delta] : plants) p.push_back({launch, row, col, delta});
+    Value v;
+    {
+      py::gil_scoped_release nogil;
+      v = bgc::gpu::Diag::instance().gemm_soak_planted(device, mm, nn, kk, launches, seed, p);
+    }
+    return v.dump();
+  }, py::arg("device"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("launches"), py::arg("seed"), py::arg("plants"));
   m.def("pcie_check", [](std::shared_ptr<PyBackend> b, int index, int hip_device, unsigned long long bytes, unsigned seed) {
     Value v;
     {

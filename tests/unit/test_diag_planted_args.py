@@ -1,0 +1,103 @@
+"""The planted variants of the GPU diagnostics (tests/gpu/test_diag_detection.py) write into device
+memory and accumulators at positions a test names, so a position outside the buffer, or a wave,
+lane, round, chain or element index out of range, must be refused on the host before the GPU is
+touched: an out-of-range plant can never become an out-of-bounds write.  The refusal comes before
+the first HIP call, which is why these run without a GPU (with one, a valid call would succeed;
+without, it would fail with a HIP error, not with "invalid arguments")."""
+import ctypes
+
+import pytest
+
+MIB = 1 << 20
+SEED = 0x5EED
+OK_ACC = (0, 0, 0, 0, 1.0)
+
+
+def _refused(call, *args):
+    with pytest.raises((RuntimeError, ValueError), match="invalid arguments"):
+        call(*args)
+
+
+def test_hbm_plant_outside_the_buffer(nat):
+    words = MIB // 4
+    _refused(nat.diag_hbm_planted, 0, MIB, SEED, [(words, 1)])
+    _refused(nat.diag_hbm_planted, 0, MIB, SEED, [(0, 1), (1 << 40, 1)])
+    # the buffer is rounded down to 16 bytes: the last three words of MIB + 12 do not exist
+    _refused(nat.diag_hbm_planted, 0, MIB + 12, SEED, [(words, 1)])
+
+
+def test_pcie_plant_outside_the_buffer(nat):
+    _refused(nat.diag_pcie_planted, 0, MIB, SEED, [(MIB // 8, 1)])
+    _refused(nat.diag_pcie_planted, 0, MIB, SEED, [(0, 1), ((1 << 64) - 1, 1)])
+
+
+def test_walk_plant_outside_its_chunk(nat):
+    chunk = 64 * MIB
+    target = 3 * chunk + 2 * MIB  # four chunks, the last of 2 MiB
+    _refused(nat.diag_hbm_walk_planted, 0, target, chunk, SEED, [(0, 4, 0, 1)])  # a fifth chunk
+    _refused(nat.diag_hbm_walk_planted, 0, target, chunk, SEED, [(0, -1, 0, 1)])
+    _refused(nat.diag_hbm_walk_planted, 0, target, chunk, SEED, [(0, 0, chunk // 8, 1)])
+    _refused(nat.diag_hbm_walk_planted, 0, target, chunk, SEED, [(0, 3, 2 * MIB // 8, 1)])  # past the short last chunk
+    _refused(nat.diag_hbm_walk_planted, 0, target, chunk, SEED, [(2, 0, 0, 1)])  # there are two passes
+    _refused(nat.diag_hbm_walk_planted, 0, target, chunk - 1, SEED, [])  # chunks of at least 64 MiB
+    _refused(nat.diag_hbm_walk_planted, 0, MIB, chunk, SEED, [])  # nothing left after rounding to 2 MiB
+
+
+@pytest.mark.parametrize("plant", [(0, 0, 64, 0, 1.0), (0, 0, -1, 0, 1.0), (0, 0, 0, 4, 1.0), (0, 0, 0, -1, 1.0),
+                                   (0, 8, 0, 0, 1.0), (0, -1, 0, 0, 1.0), (-2, 0, 0, 0, 1.0)],
+                         ids=["lane_64", "lane_-1", "i_4", "i_-1", "round_8", "round_-1", "wave_-2"])
+def test_mfma_check_plant_out_of_range(nat, plant):
+    _refused(nat.diag_mfma_planted, 0, 1, 64, SEED, [OK_ACC, plant], [])
+
+
+@pytest.mark.parametrize("plant", [(0, 64, 0, 0, 1.0), (0, 0, 4, 0, 1.0), (0, 0, -1, 0, 1.0), (0, 0, 0, 4, 1.0),
+                                   (-1, 0, 0, 0, 1.0)],
+                         ids=["lane_64", "chain_4", "chain_-1", "i_4", "wave_-1"])
+def test_mfma_rate_plant_out_of_range(nat, plant):
+    _refused(nat.diag_mfma_planted, 0, 1, 64, SEED, [], [OK_ACC, plant])
+
+
+@pytest.mark.parametrize("plant", [(0, 0, 0, 64, 0, 1.0), (0, 0, 0, 0, 4, 1.0), (0, 0, 2, 0, 0, 1.0), (4, 0, 0, 0, 0, 1.0),
+                                   (-1, 0, 0, 0, 0, 1.0)],
+                         ids=["lane_64", "i_4", "round_2", "variant_4", "variant_-1"])
+def test_lowp_check_plant_out_of_range(nat, plant):
+    _refused(nat.diag_mfma_lowp_planted, 0, 1, 64, SEED, [(3,) + OK_ACC, plant], [])
+
+
+@pytest.mark.parametrize("plant", [(0, 0, 64, 0, 0, 1.0), (0, 0, 0, 4, 0, 1.0), (0, 0, 0, 0, 4, 1.0), (2, 0, 0, 0, 0, 1.0)],
+                         ids=["lane_64", "chain_4", "i_4", "format_2"])
+def test_lowp_rate_plant_out_of_range(nat, plant):
+    _refused(nat.diag_mfma_lowp_planted, 0, 1, 64, SEED, [], [(1,) + OK_ACC, plant])
+
+
+@pytest.mark.parametrize("launches,plant", [(1, (0, 256, 0, 1.0)), (1, (0, -1, 0, 1.0)), (1, (0, 0, 512, 1.0)), (1, (0, 0, -1, 1.0)),
+                                            (3, (1, 0, 0, 1.0)), (2, (2, 0, 0, 1.0)), (2, (-1, 0, 0, 1.0))],
+                         ids=["row_m", "row_-1", "col_n", "col_-1", "launch_1_of_3", "launch_2_of_2", "launch_-1"])
+def test_soak_plant_outside_the_matrix_or_on_an_unverified_launch(nat, launches, plant):
+    _refused(nat.diag_gemm_soak_planted, 0, 256, 512, 128, launches, SEED, [(0, 0, 0, 1.0), plant])
+
+
+def test_negative_plant_count():
+    """A Python list cannot have a negative length, so this one goes to the C ABI directly."""
+    from bacchus_gpu_controller_amd.utils.build import gpu_diag_path
+
+    lib = ctypes.CDLL(gpu_diag_path())
+    lib.bgc_diag_last_error.restype = ctypes.c_char_p
+    out = ctypes.create_string_buffer(4096)  # larger than any result struct
+    plants = ctypes.create_string_buffer(4096)
+    u64, u32, i32 = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
+    calls = [
+        (lib.bgc_diag_hbm_planted, [i32(0), u64(MIB), u32(SEED), plants, i32(-1), out]),
+        (lib.bgc_diag_hbm_planted, [i32(0), u64(MIB), u32(SEED), None, i32(1), out]),  # a count without a list
+        (lib.bgc_diag_pcie_planted, [i32(0), u64(MIB), u32(SEED), plants, i32(-1), out]),
+        (lib.bgc_diag_hbm_walk_planted, [i32(0), u64(128 * MIB), u64(64 * MIB), u32(SEED), plants, i32(-1), None, i32(0), out]),
+        (lib.bgc_diag_mfma_planted, [i32(0), i32(1), i32(64), u32(SEED), plants, i32(-1), None, i32(0), out]),
+        (lib.bgc_diag_mfma_planted, [i32(0), i32(1), i32(64), u32(SEED), None, i32(0), plants, i32(-1), out]),
+        (lib.bgc_diag_mfma_lowp_planted, [i32(0), i32(1), i32(64), u32(SEED), plants, i32(-1), None, i32(0), out]),
+        (lib.bgc_diag_mfma_lowp_planted, [i32(0), i32(1), i32(64), u32(SEED), None, i32(0), plants, i32(-1), out]),
+        (lib.bgc_diag_gemm_soak_planted, [i32(0), i32(256), i32(256), i32(128), i32(1), u32(SEED), plants, i32(-1), out]),
+    ]
+    for fn, args in calls:
+        fn.restype = ctypes.c_int
+        assert fn(*args) != 0, fn.__name__
+        assert lib.bgc_diag_last_error().decode().startswith("invalid arguments"), (fn.__name__, lib.bgc_diag_last_error())
