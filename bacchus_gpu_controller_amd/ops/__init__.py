@@ -14,6 +14,8 @@ These are the only compute kernels in the framework: the reference controller ha
   column checksums (ABFT)
 * ``gemm_soak(device)`` — the sustained-throughput soak: the 8-phase ping-pong GEMM
   (256x256 tiles) for ``launches`` launches, every result checksummed
+* ``gemm(a, b)``       — the one-wave-per-tile MFMA GEMM on caller operands (A: MxK, B: KxN bf16),
+  fp32 result; the plainest use of the bf16 operand layout, for comparison with the others
 * ``gemm_tiled(a, bt)`` — the soak's kernel on caller operands (A: MxK, Bt: NxK bf16),
   fp32 result; used to check the kernel against a PyTorch fp32 product
 * ``mx_gemm(a, sa, bt, sbt, fmt)`` — the MX block-scaled matrix-core path on caller
@@ -145,6 +147,18 @@ def _bf16_bytes(x):
         pass
     f = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
     return ((f + 0x7FFF + ((f >> 16) & 1)) >> 16).astype(np.uint16).tobytes()
+
+
+def gemm(a, b, device=0):
+    """C = A @ B on the one-wave-per-tile MFMA kernel (mfma_gemm).  A is MxK, B is KxN; M and N
+    must be multiples of 16 (up to 4096) and K of 32 (up to 8192).  Returns an fp32 numpy array
+    MxN."""
+    m, k = a.shape
+    k2, n = b.shape
+    if k != k2:
+        raise ValueError(f"inner dimensions differ: A is {m}x{k}, B is {k2}x{n}")
+    c = native().diag_gemm(device, m, n, k, _bf16_bytes(a), _bf16_bytes(b))
+    return np.frombuffer(c, dtype=np.float32).reshape(m, n)
 
 
 def gemm_tiled(a, bt, device=0):
