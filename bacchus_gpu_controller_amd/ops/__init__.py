@@ -10,8 +10,8 @@ These are the only compute kernels in the framework: the reference controller ha
 * ``mfma(device)``      — exact-integer bf16 MFMA tiles on every CU + a throughput pass
 * ``mfma_lowp(device)`` — the same for the MX block-scaled fp8 / fp4 matrix-core path
   (``v_mfma_scale_f32_16x16x128_f8f6f4``), with and without E8M0 block scales
-* ``gemm_check(device)``— a bf16 GEMM on the matrix cores checked against exact row and
-  column checksums (ABFT)
+* ``gemm_check(device)``— a bf16 GEMM on the matrix cores checked element by element against
+  a double-precision product of the same operands on the host
 * ``gemm_soak(device)`` — the sustained-throughput soak: the 8-phase ping-pong GEMM
   (256x256 tiles) for ``launches`` launches, every result checksummed
 * ``gemm(a, b)``       — the one-wave-per-tile MFMA GEMM on caller operands (A: MxK, B: KxN bf16),

@@ -35,42 +35,29 @@ std::string so_dir() {
   return ".";
 }
 
+void* open_library(const std::string& path) {
+  void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+  if (!lib) throw std::runtime_error("cannot load " + path + ": " + dlerror());
+  return lib;
+}
+
 }  // namespace
 
-Diag::Diag(const std::string& path) : path_(path) {
-  lib_ = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-  if (!lib_) throw std::runtime_error("cannot load " + path + ": " + dlerror());
-  // each symbol is loaded as the type gpu_diag.h declares it with
-#define BGC_DIAG_SYM(member, name) member = reinterpret_cast<decltype(&name)>(dlsym(lib_, #name))
-  BGC_DIAG_SYM(device_count_, bgc_diag_device_count);
-  BGC_DIAG_SYM(hbm_, bgc_diag_hbm);
-  BGC_DIAG_SYM(mfma_, bgc_diag_mfma);
-  BGC_DIAG_SYM(lowp_, bgc_diag_mfma_lowp);
-  BGC_DIAG_SYM(arch_, bgc_diag_device_arch);
-  BGC_DIAG_SYM(gemm_, bgc_diag_gemm);
-  BGC_DIAG_SYM(burn_, bgc_diag_burn_dtype);
-  BGC_DIAG_SYM(pcie_, bgc_diag_pcie);
-  BGC_DIAG_SYM(soak_, bgc_diag_gemm_soak);
-  BGC_DIAG_SYM(tiled_, bgc_diag_gemm_tiled);
-  BGC_DIAG_SYM(mx_gemm_, bgc_diag_mx_gemm);
-  BGC_DIAG_SYM(walk_, bgc_diag_hbm_walk);
-  BGC_DIAG_SYM(bdf_, bgc_diag_device_bdf);
-  BGC_DIAG_SYM(hbm_planted_, bgc_diag_hbm_planted);
-  BGC_DIAG_SYM(walk_planted_, bgc_diag_hbm_walk_planted);
-  BGC_DIAG_SYM(pcie_planted_, bgc_diag_pcie_planted);
-  BGC_DIAG_SYM(mfma_planted_, bgc_diag_mfma_planted);
-  BGC_DIAG_SYM(lowp_planted_, bgc_diag_mfma_lowp_planted);
-  BGC_DIAG_SYM(soak_planted_, bgc_diag_gemm_soak_planted);
-  BGC_DIAG_SYM(last_error_, bgc_diag_last_error);
-  decltype(&bgc_diag_abi_version) abi = nullptr;
-  BGC_DIAG_SYM(abi, bgc_diag_abi_version);
-#undef BGC_DIAG_SYM
-  if (!device_count_ || !hbm_ || !mfma_ || !lowp_ || !arch_ || !gemm_ || !burn_ || !pcie_ || !soak_ || !tiled_ ||
-      !mx_gemm_ || !walk_ || !bdf_ || !hbm_planted_ || !walk_planted_ || !pcie_planted_ || !mfma_planted_ ||
-      !lowp_planted_ || !soak_planted_ || !last_error_ || !abi ||
-      abi() != BGC_DIAG_ABI_VERSION) {
+// the entry members load themselves (diag.h), each throwing if the library lacks it
+Diag::Diag(const std::string& path) : path_(path), lib_(open_library(path)) {
+  if (entry<decltype(&bgc_diag_abi_version)>("bgc_diag_abi_version")() != BGC_DIAG_ABI_VERSION) {
     throw std::runtime_error(path + " is not a compatible bgc diag library");
   }
+}
+
+void* Diag::symbol(const char* name) const {
+  void* sym = dlsym(lib_, name);
+  if (!sym) throw std::runtime_error(path_ + " is not a compatible bgc diag library: no " + name);
+  return sym;
+}
+
+void Diag::check(const char* what, int rc) const {
+  if (rc != 0) throw std::runtime_error(std::string(what) + ": " + last_error_());
 }
 
 Diag& Diag::instance(const std::string& explicit_path) {
@@ -105,10 +92,7 @@ std::string Diag::device_arch(int device) {
   return buf;
 }
 
-namespace {
-
-// The result structs as JSON: one shape for a diagnostic and its planted variant.
-json::Value hbm_json(int device, const bgc_hbm_result& r) {
+json::Value to_json(int device, const bgc_hbm_result& r) {
   json::Value v = json::Value::object();
   v["device"] = device;
   v["bytes"] = static_cast<unsigned long long>(r.bytes);
@@ -123,7 +107,7 @@ json::Value hbm_json(int device, const bgc_hbm_result& r) {
   return v;
 }
 
-json::Value mfma_json(int device, const bgc_mfma_result& r) {
+json::Value to_json(int device, const bgc_mfma_result& r) {
   json::Value v = json::Value::object();
   v["device"] = device;
   v["tiles_checked"] = static_cast<unsigned long long>(r.tiles_checked);
@@ -149,7 +133,7 @@ json::Value mfma_json(int device, const bgc_mfma_result& r) {
   return v;
 }
 
-json::Value lowp_json(int device, const bgc_lowp_result& r) {
+json::Value to_json(int device, const bgc_lowp_result& r) {
   json::Value bad = json::Value::array();
   for (int i = 0; i < r.bad_cus && i < 64; ++i) bad.push_back(r.bad_cu_keys[i]);
   const uint64_t mism = r.fp8_mismatches + r.fp8_scaled_mismatches + r.fp4_mismatches + r.fp4_scaled_mismatches;
@@ -170,14 +154,14 @@ json::Value lowp_json(int device, const bgc_lowp_result& r) {
                               {"passed", mism == 0 && r.throughput_ok != 0}});
 }
 
-json::Value pcie_json(int device, const bgc_pcie_result& r) {
+json::Value to_json(int device, const bgc_pcie_result& r) {
   return json::Value::object({{"device", device}, {"bytes", static_cast<unsigned long long>(r.bytes)},
                               {"iters", r.iters}, {"h2d_gbps", r.h2d_gbps}, {"d2h_gbps", r.d2h_gbps},
                               {"bidir_gbps", r.bidir_gbps}, {"mismatches", static_cast<unsigned long long>(r.mismatches)},
                               {"elapsed_ms", r.elapsed_ms}, {"passed", r.mismatches == 0}});
 }
 
-json::Value soak_json(int device, const bgc_soak_result& r) {
+json::Value to_json(int device, const bgc_soak_result& r) {
   return json::Value::object({{"device", device}, {"m", r.m}, {"n", r.n}, {"k", r.k}, {"launches", r.launches},
                               {"tile", r.tile}, {"kernel", r.kernel == 2 ? "pingpong" : "2buf"},
                               {"elapsed_ms", r.elapsed_ms}, {"tflops_mean", r.tflops_mean},
@@ -187,7 +171,7 @@ json::Value soak_json(int device, const bgc_soak_result& r) {
                               {"passed", r.row_mismatches == 0 && r.col_mismatches == 0}});
 }
 
-json::Value walk_json(int device, const bgc_hbm_walk_result& r) {
+json::Value to_json(int device, const bgc_hbm_walk_result& r) {
   char addr[32], flips[32];
   std::snprintf(addr, sizeof(addr), "0x%llx", static_cast<unsigned long long>(r.first_bad_addr));
   std::snprintf(flips, sizeof(flips), "0x%016llx", static_cast<unsigned long long>(r.first_bad_xor));
@@ -211,103 +195,36 @@ json::Value walk_json(int device, const bgc_hbm_walk_result& r) {
                               {"passed", r.mismatches == 0 && r.passes == 2}});
 }
 
-}  // namespace
-
 json::Value Diag::hbm(int device, uint64_t bytes, int iters, uint32_t seed) {
-  bgc_hbm_result r{};
-  if (hbm_(device, bytes, iters, seed, &r) != 0) throw std::runtime_error(std::string("hbm diag: ") + last_error_());
-  return hbm_json(device, r);
+  return call("hbm diag", hbm_, device, bytes, iters, seed);
 }
 
 json::Value Diag::mfma(int device, int waves_per_cu, int throughput_iters, uint32_t seed) {
-  bgc_mfma_result r{};
-  if (mfma_(device, waves_per_cu, throughput_iters, seed, &r) != 0) {
-    throw std::runtime_error(std::string("mfma diag: ") + last_error_());
-  }
-  return mfma_json(device, r);
+  return call("mfma diag", mfma_, device, waves_per_cu, throughput_iters, seed);
 }
 
 json::Value Diag::mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint32_t seed) {
-  bgc_lowp_result r{};
-  if (lowp_(device, waves_per_cu, throughput_iters, seed, &r) != 0) {
-    throw std::runtime_error(std::string("low-precision mfma diag: ") + last_error_());
-  }
-  return lowp_json(device, r);
+  return call("low-precision mfma diag", lowp_, device, waves_per_cu, throughput_iters, seed);
 }
 
-// Planted variants (gpu_diag.h): for tests only.
-json::Value Diag::hbm_planted(int device, uint64_t bytes, uint32_t seed, const std::vector<bgc_hbm_plant>& plants) {
-  bgc_hbm_result r{};
-  if (hbm_planted_(device, bytes, seed, plants.data(), static_cast<int>(plants.size()), &r) != 0) {
-    throw std::runtime_error(std::string("hbm diag: ") + last_error_());
-  }
-  return hbm_json(device, r);
+json::Value Diag::pcie(int device, uint64_t bytes, int iters, uint32_t seed) {
+  return call("pcie diag", pcie_, device, bytes, iters, seed);
 }
 
-json::Value Diag::hbm_walk_planted(int device, uint64_t bytes, uint64_t chunk_bytes, uint32_t seed,
-                                   const std::vector<bgc_walk_plant>& plants) {
-  bgc_hbm_walk_result r{};
-  std::vector<bgc_walk_chunk> chunks(1024);
-  if (walk_planted_(device, bytes, chunk_bytes, seed, plants.data(), static_cast<int>(plants.size()), chunks.data(),
-                    static_cast<int>(chunks.size()), &r) != 0) {
-    throw std::runtime_error(std::string("hbm walk: ") + last_error_());
-  }
-  json::Value v = walk_json(device, r);
-  json::Value list = json::Value::array();
-  for (int c = 0; c < r.chunks && c < static_cast<int>(chunks.size()); ++c) {
-    json::Value one = json::Value::array();
-    one.push_back(static_cast<unsigned long long>(chunks[static_cast<size_t>(c)].base));
-    one.push_back(static_cast<unsigned long long>(chunks[static_cast<size_t>(c)].bytes));
-    list.push_back(one);
-  }
-  v["chunk_list"] = list;
-  return v;
+json::Value Diag::gemm_soak(int device, int m, int n, int k, int launches, uint32_t seed) {
+  return call("gemm soak", soak_, device, m, n, k, launches, seed);
 }
 
-json::Value Diag::pcie_planted(int device, uint64_t bytes, uint32_t seed, const std::vector<bgc_pcie_plant>& plants) {
-  bgc_pcie_result r{};
-  if (pcie_planted_(device, bytes, seed, plants.data(), static_cast<int>(plants.size()), &r) != 0) {
-    throw std::runtime_error(std::string("pcie diag: ") + last_error_());
-  }
-  return pcie_json(device, r);
+json::Value Diag::hbm_walk(int device, double fraction, uint64_t chunk_bytes, int budget_ms, uint32_t seed) {
+  return call("hbm walk", walk_, device, fraction, chunk_bytes, budget_ms, seed);
 }
 
-json::Value Diag::mfma_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
-                               const std::vector<bgc_mfma_check_plant>& check, const std::vector<bgc_mfma_rate_plant>& rate) {
-  bgc_mfma_result r{};
-  if (mfma_planted_(device, waves_per_cu, throughput_iters, seed, check.data(), static_cast<int>(check.size()), rate.data(),
-                    static_cast<int>(rate.size()), &r) != 0) {
-    throw std::runtime_error(std::string("mfma diag: ") + last_error_());
-  }
-  return mfma_json(device, r);
-}
-
-json::Value Diag::mfma_lowp_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
-                                    const std::vector<bgc_lowp_check_plant>& check,
-                                    const std::vector<bgc_lowp_rate_plant>& rate) {
-  bgc_lowp_result r{};
-  if (lowp_planted_(device, waves_per_cu, throughput_iters, seed, check.data(), static_cast<int>(check.size()), rate.data(),
-                    static_cast<int>(rate.size()), &r) != 0) {
-    throw std::runtime_error(std::string("low-precision mfma diag: ") + last_error_());
-  }
-  return lowp_json(device, r);
-}
-
-json::Value Diag::gemm_soak_planted(int device, int m, int n, int k, int launches, uint32_t seed,
-                                    const std::vector<bgc_soak_plant>& plants) {
-  bgc_soak_result r{};
-  if (soak_planted_(device, m, n, k, launches, seed, plants.data(), static_cast<int>(plants.size()), &r) != 0) {
-    throw std::runtime_error(std::string("gemm soak: ") + last_error_());
-  }
-  return soak_json(device, r);
-}
-
+// The burn's JSON carries an argument (the dtype) and no device, so it is written out here.
 json::Value Diag::burn(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype) {
   bgc_burn_result r{};
-  if (burn_(device, duration_ms, waves_per_cu, seed, dtype, &r) != 0) {
-    throw std::runtime_error(std::string("burn: ") + last_error_());
-  }
-  return json::Value::object({{"dtype", burn_dtype_name(dtype)}, {"launches", r.launches}, {"elapsed_ms", r.elapsed_ms}, {"tflops_mean", r.tflops_mean},
+  check("burn", burn_(device, duration_ms, waves_per_cu, seed, dtype, &r));
+  return json::Value::object({{"dtype", burn_dtype_name(dtype)}, {"launches", r.launches},
+                              {"elapsed_ms", r.elapsed_ms}, {"tflops_mean", r.tflops_mean},
                               {"tflops_min", r.tflops_min}, {"tflops_first", r.tflops_first},
                               {"tflops_last", r.tflops_last}, {"tflops_max", r.tflops_max},
                               // the last launch against the best: < 1 when the GPU throttled
@@ -315,44 +232,22 @@ json::Value Diag::burn(int device, int duration_ms, int waves_per_cu, uint32_t s
                               {"mismatches", static_cast<unsigned long long>(r.mismatches)}});
 }
 
-json::Value Diag::pcie(int device, uint64_t bytes, int iters, uint32_t seed) {
-  bgc_pcie_result r{};
-  if (pcie_(device, bytes, iters, seed, &r) != 0) throw std::runtime_error(std::string("pcie diag: ") + last_error_());
-  return pcie_json(device, r);
-}
-
-json::Value Diag::gemm_soak(int device, int m, int n, int k, int launches, uint32_t seed) {
-  bgc_soak_result r{};
-  if (soak_(device, m, n, k, launches, seed, &r) != 0) throw std::runtime_error(std::string("gemm soak: ") + last_error_());
-  return soak_json(device, r);
-}
-
 void Diag::gemm(int device, int m, int n, int k, const uint16_t* a, const uint16_t* b, float* c) {
-  if (gemm_(device, m, n, k, a, b, c) != 0) throw std::runtime_error(std::string("gemm diag: ") + last_error_());
+  check("gemm diag", gemm_(device, m, n, k, a, b, c));
 }
 
 void Diag::gemm_tiled(int device, int m, int n, int k, const uint16_t* a, const uint16_t* bt, float* c) {
-  if (tiled_(device, m, n, k, a, bt, c) != 0) throw std::runtime_error(std::string("tiled gemm: ") + last_error_());
+  check("tiled gemm", tiled_(device, m, n, k, a, bt, c));
 }
 
 void Diag::mx_gemm(int device, int fmt, int m, int n, int k, const uint8_t* a, const uint8_t* a_scales,
                    const uint8_t* bt, const uint8_t* bt_scales, float* c) {
-  if (mx_gemm_(device, fmt, m, n, k, a, a_scales, bt, bt_scales, c) != 0) {
-    throw std::runtime_error(std::string("mx gemm: ") + last_error_());
-  }
-}
-
-json::Value Diag::hbm_walk(int device, double fraction, uint64_t chunk_bytes, int budget_ms, uint32_t seed) {
-  bgc_hbm_walk_result r{};
-  if (walk_(device, fraction, chunk_bytes, budget_ms, seed, &r) != 0) {
-    throw std::runtime_error(std::string("hbm walk: ") + last_error_());
-  }
-  return walk_json(device, r);
+  check("mx gemm", mx_gemm_(device, fmt, m, n, k, a, a_scales, bt, bt_scales, c));
 }
 
 std::string Diag::device_bdf(int device) {
   char buf[64] = {0};
-  if (bdf_(device, buf, sizeof(buf)) != 0) throw std::runtime_error(std::string("device bdf: ") + last_error_());
+  check("device bdf", bdf_(device, buf, sizeof(buf)));
   return buf;
 }
 
@@ -472,18 +367,30 @@ DiagFloors DiagFloors::mi355x_defaults() {
   return f;
 }
 
+const std::vector<std::pair<std::string, DiagFloors::Field>>& DiagFloors::fields() {
+#define BGC_FLOOR(field) {#field, &DiagFloors::field}
+  static const std::vector<std::pair<std::string, Field>> table = {
+      BGC_FLOOR(min_read_gbps), BGC_FLOOR(min_copy_gbps), BGC_FLOOR(min_write_gbps), BGC_FLOOR(min_mfma_tflops),
+      BGC_FLOOR(min_xcc_balance), BGC_FLOOR(min_fp8_tflops), BGC_FLOOR(min_fp4_tflops), BGC_FLOOR(min_xccs),
+      BGC_FLOOR(min_burn_tflops), BGC_FLOOR(min_burn_sustain), BGC_FLOOR(max_burn_hotspot_c),
+      BGC_FLOOR(max_burn_thermal_violation_pct), BGC_FLOOR(min_pcie_h2d_gbps), BGC_FLOOR(min_pcie_d2h_gbps),
+      BGC_FLOOR(require_full_pcie_width), BGC_FLOOR(min_pcie_speed_fraction), BGC_FLOOR(min_soak_tflops),
+      BGC_FLOOR(min_hbm_walk_coverage), BGC_FLOOR(min_node_burn_balance), BGC_FLOOR(max_node_power_w)};
+#undef BGC_FLOOR
+  return table;
+}
+
 json::Value judge_diag(const json::Value& result, const DiagFloors& fl) {
   json::Value out = result;
   json::Value failures = json::Value::array();
   auto num = [](const json::Value& v, const char* k) { return v.get(k).is_number() ? v.get(k).as_double() : 0.0; };
+  auto fail = [&](const char* format, auto... args) {
+    char buf[200];
+    std::snprintf(buf, sizeof(buf), format, args...);
+    failures.push_back(std::string(buf));
+  };
   auto floor_check = [&](const json::Value& v, const char* key, double floor, const char* what) {
-    if (floor <= 0) return;
-    const double got = num(v, key);
-    if (got < floor) {
-      char buf[160];
-      std::snprintf(buf, sizeof(buf), "%s %.0f below floor %.0f", what, got, floor);
-      failures.push_back(std::string(buf));
-    }
+    if (floor > 0 && num(v, key) < floor) fail("%s %.0f below floor %.0f", what, num(v, key), floor);
   };
   const json::Value& hbm = result.get("hbm");
   if (hbm.is_object()) {
@@ -502,10 +409,7 @@ json::Value judge_diag(const json::Value& result, const DiagFloors& fl) {
       failures.push_back(msg);
     }
     if (fl.min_hbm_walk_coverage > 0 && num(hw, "coverage_of_free") < fl.min_hbm_walk_coverage) {
-      char buf[160];
-      std::snprintf(buf, sizeof(buf), "HBM walk covered %.2f of free VRAM (floor %.2f)", num(hw, "coverage_of_free"),
-                    fl.min_hbm_walk_coverage);
-      failures.push_back(std::string(buf));
+      fail("HBM walk covered %.2f of free VRAM (floor %.2f)", num(hw, "coverage_of_free"), fl.min_hbm_walk_coverage);
     }
   }
   const json::Value& mf = result.get("mfma");
@@ -514,9 +418,7 @@ json::Value judge_diag(const json::Value& result, const DiagFloors& fl) {
     if (mf.get("throughput_ok").is_bool() && !mf.get("throughput_ok").as_bool()) failures.push_back("MFMA throughput accumulators wrong");
     floor_check(mf, "tflops", fl.min_mfma_tflops, "MFMA bf16 TFLOP/s");
     if (fl.min_xcc_balance > 0 && num(mf, "xcc_balance") < fl.min_xcc_balance) {
-      char buf[160];
-      std::snprintf(buf, sizeof(buf), "XCC balance %.2f below floor %.2f", num(mf, "xcc_balance"), fl.min_xcc_balance);
-      failures.push_back(std::string(buf));
+      fail("XCC balance %.2f below floor %.2f", num(mf, "xcc_balance"), fl.min_xcc_balance);
     }
     if (fl.min_xccs > 0 && num(mf, "xccs_seen") < fl.min_xccs) {
       failures.push_back("only " + std::to_string(static_cast<int>(num(mf, "xccs_seen"))) + " XCCs ran MFMA work");
@@ -525,11 +427,9 @@ json::Value judge_diag(const json::Value& result, const DiagFloors& fl) {
   const json::Value& lp = result.get("lowp");
   if (lp.is_object()) {
     if (num(lp, "mismatches") > 0) {
-      char buf[200];
-      std::snprintf(buf, sizeof(buf), "MX fp8/fp4 MFMA tile mismatches on %d CU(s): fp8 %.0f, fp8 scaled %.0f, fp4 %.0f, fp4 scaled %.0f",
-                    static_cast<int>(num(lp, "bad_cus")), num(lp, "fp8_mismatches"), num(lp, "fp8_scaled_mismatches"),
-                    num(lp, "fp4_mismatches"), num(lp, "fp4_scaled_mismatches"));
-      failures.push_back(std::string(buf));
+      fail("MX fp8/fp4 MFMA tile mismatches on %d CU(s): fp8 %.0f, fp8 scaled %.0f, fp4 %.0f, fp4 scaled %.0f",
+           static_cast<int>(num(lp, "bad_cus")), num(lp, "fp8_mismatches"), num(lp, "fp8_scaled_mismatches"),
+           num(lp, "fp4_mismatches"), num(lp, "fp4_scaled_mismatches"));
     }
     if (lp.get("throughput_ok").is_bool() && !lp.get("throughput_ok").as_bool()) {
       failures.push_back("MX fp8/fp4 MFMA throughput accumulators wrong");
@@ -541,28 +441,25 @@ json::Value judge_diag(const json::Value& result, const DiagFloors& fl) {
   if (burn.is_object()) {
     if (num(burn, "mismatches") > 0) failures.push_back("burn-in MFMA accumulators wrong");
     // the floor is for bf16; an fp8 / fp4 burn is held to it scaled by that path's rate
-    const std::string dt = burn.get("dtype").is_string() ? burn.get_string("dtype") : "bf16";
-    const int code = dt == "fp8" ? BGC_BURN_FP8 : dt == "fp4" ? BGC_BURN_FP4 : BGC_BURN_BF16;
+    const std::string dt = burn.get_string("dtype", "bf16");
+    int code = BGC_BURN_BF16;  // also what a dtype the burn does not know is judged as
+    try {
+      code = burn_dtype_code(dt);
+    } catch (const std::runtime_error&) {
+    }
     const std::string what = "burn-in MFMA " + (code == BGC_BURN_BF16 ? std::string() : "MX " + dt + " ") + "TFLOP/s";
     floor_check(burn, "tflops_mean", fl.min_burn_tflops * burn_dtype_rate_ratio(code), what.c_str());
     if (fl.min_burn_sustain > 0 && num(burn, "sustain") < fl.min_burn_sustain) {
-      char buf[160];
-      std::snprintf(buf, sizeof(buf), "MFMA rate sagged to %.2f of its start under sustained load (floor %.2f)",
-                    num(burn, "sustain"), fl.min_burn_sustain);
-      failures.push_back(std::string(buf));
+      fail("MFMA rate sagged to %.2f of its start under sustained load (floor %.2f)", num(burn, "sustain"),
+           fl.min_burn_sustain);
     }
     if (fl.max_burn_hotspot_c > 0 && num(burn, "max_hotspot_c") > fl.max_burn_hotspot_c) {
-      char buf[160];
-      std::snprintf(buf, sizeof(buf), "hotspot %.0f C under sustained load (limit %.0f)", num(burn, "max_hotspot_c"),
-                    fl.max_burn_hotspot_c);
-      failures.push_back(std::string(buf));
+      fail("hotspot %.0f C under sustained load (limit %.0f)", num(burn, "max_hotspot_c"), fl.max_burn_hotspot_c);
     }
     if (fl.max_burn_thermal_violation_pct > 0 &&
         num(burn, "thermal_violation_pct") > fl.max_burn_thermal_violation_pct) {
-      char buf[160];
-      std::snprintf(buf, sizeof(buf), "thermal throttling %.0f%% of the burn (limit %.0f%%)",
-                    num(burn, "thermal_violation_pct"), fl.max_burn_thermal_violation_pct);
-      failures.push_back(std::string(buf));
+      fail("thermal throttling %.0f%% of the burn (limit %.0f%%)", num(burn, "thermal_violation_pct"),
+           fl.max_burn_thermal_violation_pct);
     }
   }
   const json::Value& pc = result.get("pcie");
@@ -577,9 +474,7 @@ json::Value judge_diag(const json::Value& result, const DiagFloors& fl) {
     }
     const double sp = num(pc, "link_speed_mts"), msp = num(pc, "max_speed_mts");
     if (fl.min_pcie_speed_fraction > 0 && sp > 0 && msp > 0 && sp < fl.min_pcie_speed_fraction * msp) {
-      char buf[160];
-      std::snprintf(buf, sizeof(buf), "PCIe link at %.0f of %.0f MT/s under load", sp, msp);
-      failures.push_back(std::string(buf));
+      fail("PCIe link at %.0f of %.0f MT/s under load", sp, msp);
     }
   }
   const json::Value& sk = result.get("soak");

@@ -3,6 +3,10 @@
 
 #include <cstdint>
 #include <string>
+#include <tuple>
+#include <type_traits>
+#include <utility>
+#include <variant>
 #include <vector>
 
 #include "core/json.h"
@@ -48,6 +52,16 @@ struct DiagFloors {
   double min_node_burn_balance = 0;
   double max_node_power_w = 0;
   static DiagFloors mi355x_defaults();
+
+  // Every field above by its name: the one list behind the node agent's CONF_DIAG_<FIELD> and
+  // judge_diag's floors JSON.  A floor missing from it is not configurable.
+  using Field = std::variant<double DiagFloors::*, bool DiagFloors::*, int DiagFloors::*>;
+  static const std::vector<std::pair<std::string, Field>>& fields();
+  // read(name, field) for every field, the field as double&, bool& or int&.
+  template <class Read>
+  void apply(Read&& read) {
+    for (const auto& f : fields()) std::visit([&](auto member) { read(f.first, this->*member); }, f.second);
+  }
 };
 
 // Burn dtype names ("bf16", "fp8", "fp4") <-> BGC_BURN_*; the name throws on anything else.
@@ -60,6 +74,14 @@ double burn_dtype_rate_ratio(int code);
 // Pure verdict over one GPU's results ({"hbm":…, "mfma":…, "gemm":…}): adds "passed" and
 // "failures" (one string per violated check) to a copy of `result`.
 json::Value judge_diag(const json::Value& result, const DiagFloors& floors);
+
+// The result structs as JSON: one shape for a diagnostic and its planted variant.
+json::Value to_json(int device, const bgc_hbm_result& r);
+json::Value to_json(int device, const bgc_mfma_result& r);
+json::Value to_json(int device, const bgc_lowp_result& r);
+json::Value to_json(int device, const bgc_pcie_result& r);
+json::Value to_json(int device, const bgc_soak_result& r);
+json::Value to_json(int device, const bgc_hbm_walk_result& r);
 
 class Diag {
  public:
@@ -90,48 +112,50 @@ class Diag {
                const uint8_t* bt_scales, float* c);
   // Address-pattern walk of `fraction` of the free VRAM (see bgc_diag_hbm_walk).
   json::Value hbm_walk(int device, double fraction, uint64_t chunk_bytes, int budget_ms, uint32_t seed);
-  // Planted variants, for tests only (gpu_diag.h): the diagnostics above with wrong values
-  // written into their own data before the check, to show that they are detected.  Same JSON
-  // as the production calls (hbm_walk_planted adds "chunk_list": [[device address, bytes], ...]).
-  // Nothing in the node agent or the diag worker calls them.
-  json::Value hbm_planted(int device, uint64_t bytes, uint32_t seed, const std::vector<bgc_hbm_plant>& plants);
-  json::Value hbm_walk_planted(int device, uint64_t bytes, uint64_t chunk_bytes, uint32_t seed,
-                               const std::vector<bgc_walk_plant>& plants);
-  json::Value pcie_planted(int device, uint64_t bytes, uint32_t seed, const std::vector<bgc_pcie_plant>& plants);
-  json::Value mfma_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
-                           const std::vector<bgc_mfma_check_plant>& check, const std::vector<bgc_mfma_rate_plant>& rate);
-  json::Value mfma_lowp_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
-                                const std::vector<bgc_lowp_check_plant>& check, const std::vector<bgc_lowp_rate_plant>& rate);
-  json::Value gemm_soak_planted(int device, int m, int n, int k, int launches, uint32_t seed,
-                                const std::vector<bgc_soak_plant>& plants);
   // PCI bus id of a HIP device, lower-case ("0000:05:00.0").
   std::string device_bdf(int device);
   const std::string& path() const { return path_; }
 
+  // An entry point by name, as the type gpu_diag.h declares it with:
+  // entry<decltype(&bgc_diag_hbm)>("bgc_diag_hbm").  Throws if the library lacks it.  The methods
+  // above cover what the node agent and the diag worker run; this is how a test reaches an entry
+  // they do not load.
+  template <class Fn>
+  Fn entry(const char* name) const {
+    return reinterpret_cast<Fn>(symbol(name));
+  }
+  // Throws "<what>: <the library's last error>" unless an entry returned 0.
+  void check(const char* what, int rc) const;
+  // One run of an entry that takes (device, args..., result struct*): the result as JSON.
+  template <class... P, class... A>
+  json::Value call(const char* what, int (*fn)(P...), int device, A... args) const {
+    std::remove_pointer_t<std::tuple_element_t<sizeof...(P) - 1, std::tuple<P...>>> r{};
+    check(what, fn(device, args..., &r));
+    return to_json(device, r);
+  }
+
  private:
   explicit Diag(const std::string& path);
+  void* symbol(const char* name) const;
   std::string path_;
   void* lib_ = nullptr;
-  decltype(&bgc_diag_device_count) device_count_ = nullptr;
-  decltype(&bgc_diag_hbm) hbm_ = nullptr;
-  decltype(&bgc_diag_mfma) mfma_ = nullptr;
-  decltype(&bgc_diag_mfma_lowp) lowp_ = nullptr;
-  decltype(&bgc_diag_device_arch) arch_ = nullptr;
-  decltype(&bgc_diag_gemm) gemm_ = nullptr;
-  decltype(&bgc_diag_burn_dtype) burn_ = nullptr;
-  decltype(&bgc_diag_pcie) pcie_ = nullptr;
-  decltype(&bgc_diag_gemm_soak) soak_ = nullptr;
-  decltype(&bgc_diag_gemm_tiled) tiled_ = nullptr;
-  decltype(&bgc_diag_mx_gemm) mx_gemm_ = nullptr;
-  decltype(&bgc_diag_hbm_walk) walk_ = nullptr;
-  decltype(&bgc_diag_device_bdf) bdf_ = nullptr;
-  decltype(&bgc_diag_hbm_planted) hbm_planted_ = nullptr;
-  decltype(&bgc_diag_hbm_walk_planted) walk_planted_ = nullptr;
-  decltype(&bgc_diag_pcie_planted) pcie_planted_ = nullptr;
-  decltype(&bgc_diag_mfma_planted) mfma_planted_ = nullptr;
-  decltype(&bgc_diag_mfma_lowp_planted) lowp_planted_ = nullptr;
-  decltype(&bgc_diag_gemm_soak_planted) soak_planted_ = nullptr;
-  decltype(&bgc_diag_last_error) last_error_ = nullptr;
+  // each entry is loaded as the type gpu_diag.h declares it with, in this order, after lib_
+#define BGC_DIAG_ENTRY(member, name) decltype(&name) member = entry<decltype(&name)>(#name)
+  BGC_DIAG_ENTRY(last_error_, bgc_diag_last_error);
+  BGC_DIAG_ENTRY(device_count_, bgc_diag_device_count);
+  BGC_DIAG_ENTRY(arch_, bgc_diag_device_arch);
+  BGC_DIAG_ENTRY(bdf_, bgc_diag_device_bdf);
+  BGC_DIAG_ENTRY(hbm_, bgc_diag_hbm);
+  BGC_DIAG_ENTRY(walk_, bgc_diag_hbm_walk);
+  BGC_DIAG_ENTRY(pcie_, bgc_diag_pcie);
+  BGC_DIAG_ENTRY(mfma_, bgc_diag_mfma);
+  BGC_DIAG_ENTRY(lowp_, bgc_diag_mfma_lowp);
+  BGC_DIAG_ENTRY(burn_, bgc_diag_burn_dtype);
+  BGC_DIAG_ENTRY(soak_, bgc_diag_gemm_soak);
+  BGC_DIAG_ENTRY(gemm_, bgc_diag_gemm);
+  BGC_DIAG_ENTRY(tiled_, bgc_diag_gemm_tiled);
+  BGC_DIAG_ENTRY(mx_gemm_, bgc_diag_mx_gemm);
+#undef BGC_DIAG_ENTRY
 };
 
 }  // namespace bgc::gpu

@@ -44,34 +44,19 @@ NodeAgentConfig NodeAgentConfig::from_env(const EnvConfig& env) {
   if (c.diag_start_busy != "skip" && c.diag_start_busy != "diagnose") {
     throw std::runtime_error("CONF_DIAG_START_BUSY must be skip or diagnose, not " + c.diag_start_busy);
   }
-  c.diag_floors.min_hbm_walk_coverage = env.f64_or("diag_min_hbm_walk_coverage", c.diag_floors.min_hbm_walk_coverage);
-  c.diag_floors.min_node_burn_balance = env.f64_or("diag_min_node_burn_balance", c.diag_floors.min_node_burn_balance);
-  c.diag_floors.max_node_power_w = env.f64_or("diag_max_node_power_w", c.diag_floors.max_node_power_w);
+  c.diag_floors.apply([&](const std::string& name, auto& v) {  // CONF_DIAG_<FIELD> for every floor
+    const std::string key = "diag_" + name;
+    if constexpr (std::is_same_v<decltype(v), double&>) v = env.f64_or(key, v);
+    else if constexpr (std::is_same_v<decltype(v), bool&>) v = env.boolean_or(key, v);
+    else v = static_cast<int>(env.u64_or(key, static_cast<uint64_t>(v)));
+  });
   c.diag_burn_ms = env.u64_or("diag_burn_ms", 0);
   c.diag_burn_dtype = env.str_or("diag_burn_dtype", c.diag_burn_dtype);
   (void)burn_dtype_code(c.diag_burn_dtype);  // bf16 | fp8 | fp4, else the agent does not start
   c.diag_pcie_bytes = env.u64_or("diag_pcie_bytes", c.diag_pcie_bytes);
   c.diag_soak_size = static_cast<int>(env.u64_or("diag_soak_size", static_cast<uint64_t>(c.diag_soak_size)));
   c.diag_soak_launches = static_cast<int>(env.u64_or("diag_soak_launches", static_cast<uint64_t>(c.diag_soak_launches)));
-  c.diag_floors.min_soak_tflops = env.f64_or("diag_min_soak_tflops", c.diag_floors.min_soak_tflops);
   c.diag_lowp = env.boolean_or("diag_lowp", c.diag_lowp);
-  c.diag_floors.min_fp8_tflops = env.f64_or("diag_min_fp8_tflops", c.diag_floors.min_fp8_tflops);
-  c.diag_floors.min_fp4_tflops = env.f64_or("diag_min_fp4_tflops", c.diag_floors.min_fp4_tflops);
-  c.diag_floors.min_pcie_h2d_gbps = env.f64_or("diag_min_pcie_h2d_gbps", c.diag_floors.min_pcie_h2d_gbps);
-  c.diag_floors.min_pcie_d2h_gbps = env.f64_or("diag_min_pcie_d2h_gbps", c.diag_floors.min_pcie_d2h_gbps);
-  c.diag_floors.require_full_pcie_width = env.boolean_or("diag_require_full_pcie_width", c.diag_floors.require_full_pcie_width);
-  c.diag_floors.min_pcie_speed_fraction = env.f64_or("diag_min_pcie_speed_fraction", c.diag_floors.min_pcie_speed_fraction);
-  c.diag_floors.min_burn_tflops = env.f64_or("diag_min_burn_tflops", c.diag_floors.min_burn_tflops);
-  c.diag_floors.min_burn_sustain = env.f64_or("diag_min_burn_sustain", c.diag_floors.min_burn_sustain);
-  c.diag_floors.max_burn_hotspot_c = env.f64_or("diag_max_burn_hotspot_c", c.diag_floors.max_burn_hotspot_c);
-  c.diag_floors.max_burn_thermal_violation_pct =
-      env.f64_or("diag_max_burn_thermal_violation_pct", c.diag_floors.max_burn_thermal_violation_pct);
-  c.diag_floors.min_read_gbps = env.f64_or("diag_min_read_gbps", c.diag_floors.min_read_gbps);
-  c.diag_floors.min_copy_gbps = env.f64_or("diag_min_copy_gbps", c.diag_floors.min_copy_gbps);
-  c.diag_floors.min_write_gbps = env.f64_or("diag_min_write_gbps", c.diag_floors.min_write_gbps);
-  c.diag_floors.min_mfma_tflops = env.f64_or("diag_min_mfma_tflops", c.diag_floors.min_mfma_tflops);
-  c.diag_floors.min_xcc_balance = env.f64_or("diag_min_xcc_balance", c.diag_floors.min_xcc_balance);
-  c.diag_floors.min_xccs = static_cast<int>(env.u64_or("diag_min_xccs", static_cast<uint64_t>(c.diag_floors.min_xccs)));
   c.pod_resources_socket = env.str_or("pod_resources_socket", c.pod_resources_socket);
   HealthPolicy& h = c.health;
   h.max_hotspot_c = env.f64_or("max_hotspot_c", h.max_hotspot_c);

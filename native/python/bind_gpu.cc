@@ -74,6 +74,39 @@ bgc::gpu::HealthPolicy policy_from_json(const std::string& js) {
   return p;
 }
 
+// Runs a diagnostic (a callable that returns its JSON) with the GIL released; the JSON as text.
+template <class Run>
+std::string dump_nogil(Run&& run) {
+  Value v;
+  {
+    py::gil_scoped_release nogil;
+    v = run();
+  }
+  return v.dump();
+}
+
+// Runs a GEMM that fills an m x n fp32 C with the GIL released; C as bytes.
+template <class Run>
+py::bytes gemm_nogil(int m, int n, Run&& run) {
+  std::string c(static_cast<size_t>(m) * n * 4, '\0');
+  {
+    py::gil_scoped_release nogil;
+    run(reinterpret_cast<float*>(c.data()));
+  }
+  return py::bytes(c);
+}
+
+const uint16_t* u16(const std::string& x) { return reinterpret_cast<const uint16_t*>(x.data()); }
+const uint8_t* u8(const std::string& x) { return reinterpret_cast<const uint8_t*>(x.data()); }
+template <class T>
+int count(const std::vector<T>& v) { return static_cast<int>(v.size()); }
+
+// A planted entry run like Diag's own: "<what>: <last error>" when it fails, the result struct as JSON.
+template <class Fn, class... A>
+std::string planted(const char* what, Fn entry, A... args) {
+  return dump_nogil([&] { return bgc::gpu::Diag::instance().call(what, entry, args...); });
+}
+
 }  // namespace
 
 void register_gpu(py::module_& m) {
@@ -170,57 +203,31 @@ void register_gpu(py::module_& m) {
      py::arg("policy") = "{}", py::arg("page_limit") = 0);
 
   // --- HIP diagnostics ---
-  m.def("diag_library_path", [](const std::string& p) { return bgc::gpu::Diag::instance(p).path(); },
-        py::arg("explicit_path") = "");
-  m.def("diag_device_count", [] { return bgc::gpu::Diag::instance().device_count(); });
-  m.def("diag_device_arch", [](int d) { return bgc::gpu::Diag::instance().device_arch(d); });
+  using bgc::gpu::Diag;
+  m.def("diag_library_path", [](const std::string& p) { return Diag::instance(p).path(); }, py::arg("explicit_path") = "");
+  m.def("diag_device_count", [] { return Diag::instance().device_count(); });
+  m.def("diag_device_arch", [](int d) { return Diag::instance().device_arch(d); });
+  m.def("diag_device_bdf", [](int d) { return Diag::instance().device_bdf(d); });
   m.def("diag_hbm", [](int device, unsigned long long bytes, int iters, unsigned seed) {
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::Diag::instance().hbm(device, bytes, iters, seed);
-    }
-    return v.dump();
+    return dump_nogil([&] { return Diag::instance().hbm(device, bytes, iters, seed); });
   }, py::arg("device"), py::arg("bytes") = 2ULL << 30, py::arg("iters") = 3, py::arg("seed") = 0x5eed);
   m.def("diag_mfma", [](int device, int waves_per_cu, int iters, unsigned seed) {
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::Diag::instance().mfma(device, waves_per_cu, iters, seed);
-    }
-    return v.dump();
+    return dump_nogil([&] { return Diag::instance().mfma(device, waves_per_cu, iters, seed); });
   }, py::arg("device"), py::arg("waves_per_cu") = 32, py::arg("iters") = 4096, py::arg("seed") = 0x5eed);
   m.def("diag_mfma_lowp", [](int device, int waves_per_cu, int iters, unsigned seed) {
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::Diag::instance().mfma_lowp(device, waves_per_cu, iters, seed);
-    }
-    return v.dump();
+    return dump_nogil([&] { return Diag::instance().mfma_lowp(device, waves_per_cu, iters, seed); });
   }, py::arg("device"), py::arg("waves_per_cu") = 32, py::arg("iters") = 4096, py::arg("seed") = 0x5eed);
   m.def("diag_gemm", [](int device, int mm, int nn, int kk, const std::string& a, const std::string& b) {
     if (a.size() != static_cast<size_t>(mm) * kk * 2 || b.size() != static_cast<size_t>(kk) * nn * 2) {
       throw std::invalid_argument("A must be M*K and B K*N bf16 values");
     }
-    std::string c(static_cast<size_t>(mm) * nn * 4, '\0');
-    {
-      py::gil_scoped_release nogil;
-      bgc::gpu::Diag::instance().gemm(device, mm, nn, kk, reinterpret_cast<const uint16_t*>(a.data()),
-                                      reinterpret_cast<const uint16_t*>(b.data()), reinterpret_cast<float*>(c.data()));
-    }
-    return py::bytes(c);
+    return gemm_nogil(mm, nn, [&](float* c) { Diag::instance().gemm(device, mm, nn, kk, u16(a), u16(b), c); });
   }, py::arg("device"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("a_bf16"), py::arg("b_bf16"));
   m.def("diag_gemm_tiled", [](int device, int mm, int nn, int kk, const std::string& a, const std::string& bt) {
     if (a.size() != static_cast<size_t>(mm) * kk * 2 || bt.size() != static_cast<size_t>(nn) * kk * 2) {
       throw std::invalid_argument("A must be M*K and Bt N*K bf16 values");
     }
-    std::string c(static_cast<size_t>(mm) * nn * 4, '\0');
-    {
-      py::gil_scoped_release nogil;
-      bgc::gpu::Diag::instance().gemm_tiled(device, mm, nn, kk, reinterpret_cast<const uint16_t*>(a.data()),
-                                            reinterpret_cast<const uint16_t*>(bt.data()), reinterpret_cast<float*>(c.data()));
-    }
-    return py::bytes(c);
+    return gemm_nogil(mm, nn, [&](float* c) { Diag::instance().gemm_tiled(device, mm, nn, kk, u16(a), u16(bt), c); });
   }, py::arg("device"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("a_bf16"), py::arg("bt_bf16"));
   m.def("diag_mx_gemm", [](int device, int fmt, int mm, int nn, int kk, const std::string& a, const std::string& sa,
                            const std::string& bt, const std::string& sb) {
@@ -230,95 +237,62 @@ void register_gpu(py::module_& m) {
         sb.size() != static_cast<size_t>(nn) * (kk / 32)) {
       throw std::invalid_argument("fmt 0: A M*K, Bt N*K bytes; fmt 4: M*K/2, N*K/2; scales M*K/32 and N*K/32 bytes");
     }
-    std::string c(static_cast<size_t>(mm) * nn * 4, '\0');
-    {
-      py::gil_scoped_release nogil;
-      auto u8 = [](const std::string& x) { return reinterpret_cast<const uint8_t*>(x.data()); };
-      bgc::gpu::Diag::instance().mx_gemm(device, fmt, mm, nn, kk, u8(a), u8(sa), u8(bt), u8(sb),
-                                         reinterpret_cast<float*>(c.data()));
-    }
-    return py::bytes(c);
+    return gemm_nogil(mm, nn, [&](float* c) {
+      Diag::instance().mx_gemm(device, fmt, mm, nn, kk, u8(a), u8(sa), u8(bt), u8(sb), c);
+    });
   }, py::arg("device"), py::arg("fmt"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("a"), py::arg("a_scales"),
      py::arg("bt"), py::arg("bt_scales"));
   m.def("diag_hbm_walk", [](int device, double fraction, unsigned long long chunk_bytes, int budget_ms, unsigned seed) {
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::Diag::instance().hbm_walk(device, fraction, chunk_bytes, budget_ms, seed);
-    }
-    return v.dump();
+    return dump_nogil([&] { return Diag::instance().hbm_walk(device, fraction, chunk_bytes, budget_ms, seed); });
   }, py::arg("device"), py::arg("fraction") = 0.9, py::arg("chunk_bytes") = 4ULL << 30, py::arg("budget_ms") = 20000,
      py::arg("seed") = 0x5eed);
-  m.def("diag_device_bdf", [](int d) { return bgc::gpu::Diag::instance().device_bdf(d); });
   m.def("diag_gemm_check", [](int device, int mm, int nn, int kk, unsigned seed) {
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::Diag::instance().gemm_check(device, mm, nn, kk, seed);
-    }
-    return v.dump();
+    return dump_nogil([&] { return Diag::instance().gemm_check(device, mm, nn, kk, seed); });
   }, py::arg("device"), py::arg("m") = 64, py::arg("n") = 64, py::arg("k") = 512, py::arg("seed") = 0x5eed);
   m.def("diag_burn", [](std::shared_ptr<PyBackend> b, int index, int hip_device, int duration_ms, unsigned seed,
                         const std::string& dtype) {
     const int code = bgc::gpu::burn_dtype_code(dtype);
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::burn_in(*b->b, index, hip_device, duration_ms, seed, nullptr, code);
-    }
-    return v.dump();
+    return dump_nogil([&] { return bgc::gpu::burn_in(*b->b, index, hip_device, duration_ms, seed, nullptr, code); });
   }, py::arg("backend"), py::arg("index"), py::arg("hip_device"), py::arg("duration_ms"), py::arg("seed") = 0x5eed,
      py::arg("dtype") = "bf16");
   m.def("diag_pcie", [](int device, unsigned long long bytes, int iters, unsigned seed) {
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::Diag::instance().pcie(device, bytes, iters, seed);
-    }
-    return v.dump();
+    return dump_nogil([&] { return Diag::instance().pcie(device, bytes, iters, seed); });
   }, py::arg("device"), py::arg("bytes") = 256ULL << 20, py::arg("iters") = 5, py::arg("seed") = 0x5eed);
   m.def("diag_gemm_soak", [](int device, int mm, int nn, int kk, int launches, unsigned seed) {
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::Diag::instance().gemm_soak(device, mm, nn, kk, launches, seed);
-    }
-    return v.dump();
+    return dump_nogil([&] { return Diag::instance().gemm_soak(device, mm, nn, kk, launches, seed); });
   }, py::arg("device"), py::arg("m") = 8192, py::arg("n") = 8192, py::arg("k") = 8192, py::arg("launches") = 10,
      py::arg("seed") = 0x5eed);
-  // Planted variants (gpu_diag.h): for tests only.  Plants are lists of tuples in the order of the
-  // C structs' fields; the library checks them ("invalid arguments") before it touches the GPU.
+  // Planted variants (gpu_diag.h): for tests only, so only these bindings resolve their entries, at the
+  // call.  Plants are lists of tuples in the order of the C structs' fields; the library checks them
+  // ("invalid arguments") before it touches the GPU.
+#define BGC_DIAG_ENTRY(name) Diag::instance().entry<decltype(&name)>(#name)
   using u64 = unsigned long long;
   m.def("diag_hbm_planted", [](int device, u64 bytes, unsigned seed, const std::vector<std::tuple<u64, unsigned>>& plants) {
     std::vector<bgc_hbm_plant> p;
     for (const auto& [word, mask] : plants) p.push_back({word, mask});
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::Diag::instance().hbm_planted(device, bytes, seed, p);
-    }
-    return v.dump();
+    return planted("hbm diag", BGC_DIAG_ENTRY(bgc_diag_hbm_planted), device, bytes, seed, p.data(), count(p));
   }, py::arg("device"), py::arg("bytes"), py::arg("seed"), py::arg("plants"));
   m.def("diag_hbm_walk_planted", [](int device, u64 bytes, u64 chunk_bytes, unsigned seed,
                                     const std::vector<std::tuple<int, int, u64, u64>>& plants) {
     std::vector<bgc_walk_plant> p;
     for (const auto& [pass, chunk, offset, mask] : plants) p.push_back({pass, chunk, offset, mask});
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::Diag::instance().hbm_walk_planted(device, bytes, chunk_bytes, seed, p);
-    }
-    return v.dump();
+    std::vector<bgc_walk_chunk> chunks(1024);
+    return dump_nogil([&] {
+      Value v = Diag::instance().call("hbm walk", BGC_DIAG_ENTRY(bgc_diag_hbm_walk_planted), device, bytes, chunk_bytes,
+                                      seed, p.data(), count(p), chunks.data(), count(chunks));
+      Value list = Value::array();  // the walk's result plus "chunk_list": [[device address, bytes], ...]
+      for (int c = 0; c < v.get("chunks").as_int() && c < count(chunks); ++c) {
+        const bgc_walk_chunk& one = chunks[static_cast<size_t>(c)];
+        list.push_back(Value::array({static_cast<u64>(one.base), static_cast<u64>(one.bytes)}));
+      }
+      v["chunk_list"] = list;
+      return v;
+    });
   }, py::arg("device"), py::arg("bytes"), py::arg("chunk_bytes"), py::arg("seed"), py::arg("plants"));
   m.def("diag_pcie_planted", [](int device, u64 bytes, unsigned seed, const std::vector<std::tuple<u64, u64>>& plants) {
     std::vector<bgc_pcie_plant> p;
     for (const auto& [word, mask] : plants) p.push_back({word, mask});
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::Diag::instance().pcie_planted(device, bytes, seed, p);
-    }
-    return v.dump();
+    return planted("pcie diag", BGC_DIAG_ENTRY(bgc_diag_pcie_planted), device, bytes, seed, p.data(), count(p));
   }, py::arg("device"), py::arg("bytes"), py::arg("seed"), py::arg("plants"));
   using AccPlant = std::tuple<int, int, int, int, float>;       // check: wave, round, lane, i, delta; rate: wave, lane, chain, i, delta
   using LowpPlant = std::tuple<int, int, int, int, int, float>;  // the variant (check) or format (rate) in front
@@ -328,12 +302,8 @@ void register_gpu(py::module_& m) {
     std::vector<bgc_mfma_rate_plant> r;
     for (const auto& [wave, round, lane, i, delta] : check) c.push_back({wave, round, lane, i, delta});
     for (const auto& [wave, lane, chain, i, delta] : rate) r.push_back({wave, lane, chain, i, delta});
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::Diag::instance().mfma_planted(device, waves_per_cu, iters, seed, c, r);
-    }
-    return v.dump();
+    return planted("mfma diag", BGC_DIAG_ENTRY(bgc_diag_mfma_planted), device, waves_per_cu, iters, seed, c.data(), count(c),
+                   r.data(), count(r));
   }, py::arg("device"), py::arg("waves_per_cu"), py::arg("iters"), py::arg("seed"), py::arg("check_plants"),
      py::arg("rate_plants"));
   m.def("diag_mfma_lowp_planted", [](int device, int waves_per_cu, int iters, unsigned seed, const std::vector<LowpPlant>& check,
@@ -342,61 +312,38 @@ void register_gpu(py::module_& m) {
     std::vector<bgc_lowp_rate_plant> r;
     for (const auto& [variant, wave, round, lane, i, delta] : check) c.push_back({variant, {wave, round, lane, i, delta}});
     for (const auto& [fmt, wave, lane, chain, i, delta] : rate) r.push_back({fmt, {wave, lane, chain, i, delta}});
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::Diag::instance().mfma_lowp_planted(device, waves_per_cu, iters, seed, c, r);
-    }
-    return v.dump();
+    return planted("low-precision mfma diag", BGC_DIAG_ENTRY(bgc_diag_mfma_lowp_planted), device, waves_per_cu, iters, seed,
+                   c.data(), count(c), r.data(), count(r));
   }, py::arg("device"), py::arg("waves_per_cu"), py::arg("iters"), py::arg("seed"), py::arg("check_plants"),
      py::arg("rate_plants"));
   m.def("diag_gemm_soak_planted", [](int device, int mm, int nn, int kk, int launches, unsigned seed,
                                      const std::vector<std::tuple<int, int, int, float>>& plants) {
     std::vector<bgc_soak_plant> p;
     for (const auto& [launch, row, col, delta] : plants) p.push_back({launch, row, col, delta});
-    Value v;
-    {
-      py::gil_scoped_release nogil;
-      v = bgc::gpu::Diag::instance().gemm_soak_planted(device, mm, nn, kk, launches, seed, p);
-    }
-    return v.dump();
+    return planted("gemm soak", BGC_DIAG_ENTRY(bgc_diag_gemm_soak_planted), device, mm, nn, kk, launches, seed, p.data(),
+                   count(p));
   }, py::arg("device"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("launches"), py::arg("seed"), py::arg("plants"));
+#undef BGC_DIAG_ENTRY
   m.def("pcie_check", [](std::shared_ptr<PyBackend> b, int index, int hip_device, unsigned long long bytes, unsigned seed) {
-    Value v;
-    {
-      py::gil_scoped_release nogil;
+    return dump_nogil([&] {
       auto gpus = b->b->discover();
       if (index < 0 || static_cast<size_t>(index) >= gpus.size()) throw std::out_of_range("no such GPU");
-      v = bgc::gpu::pcie_check(*b->b, gpus[static_cast<size_t>(index)], hip_device, bytes, seed);
-    }
-    return v.dump();
+      return bgc::gpu::pcie_check(*b->b, gpus[static_cast<size_t>(index)], hip_device, bytes, seed);
+    });
   }, py::arg("backend"), py::arg("index"), py::arg("hip_device"), py::arg("bytes") = 256ULL << 20, py::arg("seed") = 0x5eed);
   m.def("judge_diag", [](const std::string& result, const std::string& floors_json) {
     bgc::gpu::DiagFloors f = bgc::gpu::DiagFloors::mi355x_defaults();
-    Value fj = bgc::json::parse(floors_json);
-    auto num = [&](const char* k, double& dst) {
-      if (fj.get(k).is_number()) dst = fj.get(k).as_double();
-    };
-    num("min_read_gbps", f.min_read_gbps);
-    num("min_copy_gbps", f.min_copy_gbps);
-    num("min_write_gbps", f.min_write_gbps);
-    num("min_mfma_tflops", f.min_mfma_tflops);
-    num("min_xcc_balance", f.min_xcc_balance);
-    num("min_fp8_tflops", f.min_fp8_tflops);
-    num("min_fp4_tflops", f.min_fp4_tflops);
-    num("min_burn_tflops", f.min_burn_tflops);
-    num("min_burn_sustain", f.min_burn_sustain);
-    num("max_burn_hotspot_c", f.max_burn_hotspot_c);
-    num("max_burn_thermal_violation_pct", f.max_burn_thermal_violation_pct);
-    num("min_pcie_h2d_gbps", f.min_pcie_h2d_gbps);
-    num("min_pcie_d2h_gbps", f.min_pcie_d2h_gbps);
-    num("min_pcie_speed_fraction", f.min_pcie_speed_fraction);
-    num("min_soak_tflops", f.min_soak_tflops);
-    num("min_hbm_walk_coverage", f.min_hbm_walk_coverage);
-    num("min_node_burn_balance", f.min_node_burn_balance);
-    num("max_node_power_w", f.max_node_power_w);
-    if (fj.get("require_full_pcie_width").is_bool()) f.require_full_pcie_width = fj.get("require_full_pcie_width").as_bool();
-    if (fj.get("min_xccs").is_int()) f.min_xccs = static_cast<int>(fj.get("min_xccs").as_int());
+    const Value fj = bgc::json::parse(floors_json);
+    f.apply([&](const std::string& name, auto& v) {  // a floor of another JSON type than its field is ignored
+      const Value& j = fj.get(name);
+      if constexpr (std::is_same_v<decltype(v), double&>) {
+        if (j.is_number()) v = j.as_double();
+      } else if constexpr (std::is_same_v<decltype(v), bool&>) {
+        if (j.is_bool()) v = j.as_bool();
+      } else if (j.is_int()) {
+        v = static_cast<int>(j.as_int());
+      }
+    });
     return bgc::gpu::judge_diag(bgc::json::parse(result), f).dump();
   }, py::arg("result"), py::arg("floors") = "{}");
   m.def("roctx_available", &bgc::roctx::available);

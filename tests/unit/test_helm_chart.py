@@ -8,6 +8,7 @@ and the chart name.
 """
 import json
 import os
+import re
 import subprocess
 
 import pytest
@@ -325,6 +326,11 @@ def test_every_node_agent_config_key_reaches_the_binary():
     for fn in ("native/gpu/node_agent.cc", "native/bin/node_agent.cc", "native/kube/runtime.cc"):
         with open(os.path.join(REPO_ROOT, fn)) as f:
             src += f.read()
+    # the diagnostics' floors are read as "diag_" + the name of each entry of DiagFloors' field table
+    with open(os.path.join(REPO_ROOT, "native/gpu/diag.cc")) as f:
+        table = f.read().split("DiagFloors::fields() {")[1].split("return table;")[0]
+    assert '"diag_" + name' in src
+    src += "".join(f' "diag_{name}"' for name in re.findall(r"BGC_FLOOR\((\w+)\)", table))
     for k, v in keys.items():
         if k == "rust_log":
             assert env["RUST_LOG"] == v
