@@ -3,15 +3,22 @@
 // throughput kernels back to back (bgc_diag_burn_dtype), and the one-wave-per-tile GEMMs on
 // caller operands (bgc_diag_gemm, bgc_diag_mx_gemm).
 //
-//  * The MFMA test runs one v_mfma_f32_16x16x32_bf16 tile per wave per round with
-//    operands in {-1,0,1} generated from a hash in registers (no memory traffic), so
-//    every product sum is an exact fp32 integer and is checked element-wise against a
+//  * A tile trait (Bf16Tile, MxTile<fmt>) says what differs between the matrix-core paths: how a
+//    lane's operands are packed, the MFMA, and the exact value of one output element.  One check
+//    kernel (mfma_check) and one throughput kernel (mfma_throughput) are instantiated over them.
+//  * The check runs one MFMA tile per wave per round with operands in {-1,0,1} (and, for MX,
+//    block scales in {1/2,1,2}) generated from a hash in registers (no memory traffic), so
+//    every product sum is an exact fp32 value and is checked element-wise against a
 //    VALU recomputation.  Each wave records its physical CU (HW_REG_XCC_ID + HW_ID),
 //    so a faulty matrix core is attributed to (XCC, SE, SH, CU).
 //  * The throughput phase chains 4 independent accumulators per wave (dependent MFMA
 //    latency hidden by 8 waves/SIMD) and verifies acc == iters * tile exactly.
+//  * On the host, bgc_diag_mfma and bgc_diag_mfma_lowp share the per-CU bins (CuBins), the test
+//    plants (HostPlants) and the choice between a kernel's production and planted instantiation
+//    (with_plants); each fills its own result struct.
 #include <algorithm>
 #include <cstring>
+#include <utility>
 
 #include "diag_common.h"
 
@@ -39,6 +46,9 @@ __device__ __forceinline__ uint32_t cu_key() {
 // (l & 15) and of B column (l & 15) from lane group l >> 4; the result lane l holds column
 // (l & 15), rows 4 (l >> 4) + i (the C/D map of every 16x16 MFMA).  A element (row, k) is
 // operand(seed, tile, row, k, 0xA); B element (k, col) is b_operand(seed, tile, k, col).
+// mfma() takes the lane's two scale exponents, scale_exp() of its (row or column, lane group), and
+// expect() is the exact fp32 value of output element (row, col); a tile without block scales
+// ignores `scaled`.
 
 // v_mfma_f32_16x16x32_bf16: A is 16x32, B is 32x16, lane group g holds k = 8 g + j.
 struct Bf16Tile {
@@ -53,11 +63,17 @@ struct Bf16Tile {
     }
     return v;
   }
-  static __device__ __forceinline__ f32x4 mfma(Frag a, Frag b, f32x4 acc) {
+  static __device__ __forceinline__ f32x4 mfma(Frag a, Frag b, f32x4 acc, int /*sa*/, int /*sb*/) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
   }
   static __device__ __forceinline__ int b_operand(uint32_t seed, uint32_t tile, int k, int col) {
     return operand(seed, tile, k, col, 0xB);
+  }
+  static __device__ __forceinline__ int scale_exp(uint32_t, uint32_t, int, int, uint32_t, bool) { return 0; }
+  static __device__ __forceinline__ float expect(uint32_t seed, uint32_t tile, int row, int col, bool /*scaled*/) {
+    int dot = 0;
+    for (int k = 0; k < kK; ++k) dot += operand(seed, tile, row, k, 0xA) * b_operand(seed, tile, k, col);
+    return static_cast<float>(dot);
   }
 };
 
@@ -90,12 +106,7 @@ __device__ __forceinline__ int lowp_exp(uint32_t seed, uint32_t tile, int rc, in
   return scaled ? operand(seed ^ 0x5ca1e, tile, rc, g, which) : 0;
 }
 
-template <int kFmt>
-__device__ __forceinline__ f32x4 lowp_mfma(i32x8 a, i32x8 b, f32x4 acc, int sa, int sb) {
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, kFmt, kFmt, 0, 127 + sa, 0, 127 + sb);
-}
-
-// the MX tile with unit scales: both operands are indexed (row or column, k)
+// the MX tile: both operands are indexed (row or column, k)
 template <int kFmt>
 struct MxTile {
   using Frag = i32x8;
@@ -114,29 +125,27 @@ struct MxTile {
     }
     return v;
   }
-  static __device__ __forceinline__ f32x4 mfma(Frag a, Frag b, f32x4 acc) { return lowp_mfma<kFmt>(a, b, acc, 0, 0); }
+  static __device__ __forceinline__ f32x4 mfma(Frag a, Frag b, f32x4 acc, int sa, int sb) {
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, kFmt, kFmt, 0, 127 + sa, 0, 127 + sb);
+  }
   static __device__ __forceinline__ int b_operand(uint32_t seed, uint32_t tile, int k, int col) {
     return operand(seed, tile, col, k, 0xB);
   }
-};
-
-// ---------------------------------------------------------------------------
-// Check kernels: wave w checks tiles w * rounds .. w * rounds + rounds - 1 element-wise and bins
-// the outcome by the CU it runs on.
-struct CheckWave {
-  int lane;
-  uint32_t wave, key;
-  __device__ __forceinline__ CheckWave()
-      : lane(threadIdx.x & 63), wave((blockIdx.x * (kBlock / 64)) + (threadIdx.x >> 6)), key(cu_key()) {}
-  __device__ __forceinline__ uint32_t tile(int rounds, int r) const {
-    return wave * static_cast<uint32_t>(rounds) + static_cast<uint32_t>(r);
+  static __device__ __forceinline__ int scale_exp(uint32_t seed, uint32_t tile, int rc, int g, uint32_t which, bool scaled) {
+    return lowp_exp(seed, tile, rc, g, which, scaled);
   }
-  // one atomic per wave: `bad` is the wave's sum of wrong elements, in lane 0
-  __device__ __forceinline__ void report(int rounds, unsigned bad, unsigned* cu_tiles, unsigned* cu_bad) const {
-    if (lane == 0) {
-      atomicAdd(&cu_tiles[key], static_cast<unsigned>(rounds));
-      if (bad) atomicAdd(&cu_bad[key], bad);
+  static __device__ __forceinline__ float expect(uint32_t seed, uint32_t tile, int row, int col, bool scaled) {
+    int dot[4] = {0, 0, 0, 0};  // per scale block
+    for (int g = 0; g < 4; ++g) {
+      for (int j = 0; j < 32; ++j) {
+        dot[lowp_block<kFmt>(g, j)] += operand(seed, tile, row, 32 * g + j, 0xA) * b_operand(seed, tile, 32 * g + j, col);
+      }
     }
+    float e = 0.f;
+    for (int blk = 0; blk < 4; ++blk) {
+      e += ldexpf(static_cast<float>(dot[blk]), scale_exp(seed, tile, row, blk, 0xA, scaled) + scale_exp(seed, tile, col, blk, 0xB, scaled));
+    }
+    return e;
   }
 };
 
@@ -144,15 +153,14 @@ struct CheckWave {
 // `Plants... plants`: empty in the production instantiations, which so take no further argument and
 // call the empty plant() overloads (they compile to what they would be without), and one plant list
 // in the instantiations behind the *_planted entry points.  Everything else, the comparison, the
-// wave reduction and the report, is the same source for both.
-struct CheckPlants {
-  const bgc_mfma_check_plant* p;
-  int n;
-};
-struct RatePlants {
-  const bgc_mfma_rate_plant* p = nullptr;
+// wave reduction and the report, is the same source for both; with_plants() below picks between them.
+template <class P>
+struct PlantList {  // in device memory
+  const P* p = nullptr;
   int n = 0;
 };
+using CheckPlants = PlantList<bgc_mfma_check_plant>;
+using RatePlants = PlantList<bgc_mfma_rate_plant>;
 
 __device__ __forceinline__ void add_at(f32x4& acc, int i, float delta) {
 #pragma unroll
@@ -185,64 +193,31 @@ __device__ __forceinline__ void plant(f32x4 (&acc)[4], uint32_t wave, int lane, 
   }
 }
 
-template <class... Plants>
-__global__ __launch_bounds__(kBlock) void mfma_check(uint32_t seed, int rounds, unsigned* __restrict__ cu_tiles,
+// ---------------------------------------------------------------------------
+// Check: wave w checks tiles w * rounds .. w * rounds + rounds - 1 element-wise, with the tile's
+// block scales if `scaled`, and bins the outcome by the CU it runs on.
+template <class Tile, class... Plants>
+__global__ __launch_bounds__(kBlock) void mfma_check(uint32_t seed, int rounds, int scaled, unsigned* __restrict__ cu_tiles,
                                                      unsigned* __restrict__ cu_bad, Plants... plants) {
-  const CheckWave w;
-  const int rc = w.lane & 15, g = w.lane >> 4;
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = (blockIdx.x * (kBlock / 64)) + (threadIdx.x >> 6), key = cu_key();
+  const int rc = lane & 15, g = lane >> 4;
   unsigned bad = 0;
   for (int r = 0; r < rounds; ++r) {
-    const uint32_t tile = w.tile(rounds, r);
-    const bf16x8 a = Bf16Tile::pack(seed, tile, rc, g, 0xA);
-    const bf16x8 b = Bf16Tile::pack(seed, tile, rc, g, 0xB);
-    f32x4 acc = Bf16Tile::mfma(a, b, f32x4{0.f, 0.f, 0.f, 0.f});
-    plant(acc, w.wave, r, w.lane, plants...);
+    const uint32_t tile = wave * static_cast<uint32_t>(rounds) + static_cast<uint32_t>(r);
+    const typename Tile::Frag a = Tile::pack(seed, tile, rc, g, 0xA);
+    const typename Tile::Frag b = Tile::pack(seed, tile, rc, g, 0xB);
+    f32x4 acc = Tile::mfma(a, b, f32x4{0.f, 0.f, 0.f, 0.f}, Tile::scale_exp(seed, tile, rc, g, 0xA, scaled),
+                           Tile::scale_exp(seed, tile, rc, g, 0xB, scaled));
+    plant(acc, wave, r, lane, plants...);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int orow = 4 * g + i;
-      int expect = 0;
-      for (int k = 0; k < 32; ++k) expect += operand(seed, tile, orow, k, 0xA) * Bf16Tile::b_operand(seed, tile, k, rc);
-      bad += (acc[i] != static_cast<float>(expect));
-    }
+    for (int i = 0; i < 4; ++i) bad += (acc[i] != Tile::expect(seed, tile, 4 * g + i, rc, scaled));
   }
-  for (int off = 32; off > 0; off >>= 1) bad += __shfl_down(bad, off, 64);
-  w.report(rounds, bad, cu_tiles, cu_bad);
-}
-
-template <int kFmt, class... Plants>
-__global__ __launch_bounds__(kBlock) void mfma_lowp_check(uint32_t seed, int rounds, int scaled,
-                                                          unsigned* __restrict__ cu_tiles,
-                                                          unsigned* __restrict__ cu_bad, Plants... plants) {
-  const CheckWave w;
-  const int rc = w.lane & 15, g = w.lane >> 4;
-  unsigned bad = 0;
-  for (int r = 0; r < rounds; ++r) {
-    const uint32_t tile = w.tile(rounds, r);
-    const i32x8 a = MxTile<kFmt>::pack(seed, tile, rc, g, 0xA);
-    const i32x8 b = MxTile<kFmt>::pack(seed, tile, rc, g, 0xB);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = lowp_mfma<kFmt>(a, b, acc, lowp_exp(seed, tile, rc, g, 0xA, scaled), lowp_exp(seed, tile, rc, g, 0xB, scaled));
-    plant(acc, w.wave, r, w.lane, plants...);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int orow = 4 * g + i;
-      int dot[4] = {0, 0, 0, 0};  // per scale block
-      for (int gg = 0; gg < 4; ++gg) {
-        for (int j = 0; j < 32; ++j) {
-          dot[lowp_block<kFmt>(gg, j)] +=
-              operand(seed, tile, orow, 32 * gg + j, 0xA) * operand(seed, tile, rc, 32 * gg + j, 0xB);
-        }
-      }
-      float expect = 0.f;
-      for (int blk = 0; blk < 4; ++blk) {
-        const int e = lowp_exp(seed, tile, orow, blk, 0xA, scaled) + lowp_exp(seed, tile, rc, blk, 0xB, scaled);
-        expect += ldexpf(static_cast<float>(dot[blk]), e);
-      }
-      bad += (acc[i] != expect);
-    }
+  for (int off = 32; off > 0; off >>= 1) bad += __shfl_down(bad, off, 64);  // the wave's sum, in lane 0
+  if (lane == 0) {  // one atomic per wave
+    atomicAdd(&cu_tiles[key], static_cast<unsigned>(rounds));
+    if (bad) atomicAdd(&cu_bad[key], bad);
   }
-  for (int off = 32; off > 0; off >>= 1) bad += __shfl_down(bad, off, 64);
-  w.report(rounds, bad, cu_tiles, cu_bad);
 }
 
 // ---------------------------------------------------------------------------
@@ -267,16 +242,13 @@ __global__ __launch_bounds__(kBlock) void mfma_throughput(uint32_t seed, int ite
   for (int c = 0; c < 4; ++c) acc[c] = f32x4{float(c), float(c), float(c), float(c)};
   for (int it = 0; it < iters; ++it) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) acc[c] = Tile::mfma(a, b, acc[c]);
+    for (int c = 0; c < 4; ++c) acc[c] = Tile::mfma(a, b, acc[c], 0, 0);
   }
   plant(acc, tile, lane, plants...);
   unsigned bad = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int orow = 4 * g + i;
-    int expect = 0;
-    for (int k = 0; k < Tile::kK; ++k) expect += operand(seed, tile, orow, k, 0xA) * Tile::b_operand(seed, tile, k, rc);
-    const float e = static_cast<float>(expect) * static_cast<float>(iters);
+    const float e = Tile::expect(seed, tile, 4 * g + i, rc, false) * static_cast<float>(iters);
 #pragma unroll
     for (int c = 0; c < 4; ++c) bad += (acc[c][i] != e + float(c));
   }
@@ -371,15 +343,30 @@ void with_mx_fmt(int fmt, F&& f) {
   }
 }
 
-// the production instantiation, or with test plants the planted one
+// `launch(plants...)`: of the production instantiation, or with test plants of the planted one
+template <class P, class Launch>
+void with_plants(PlantList<P> plants, Launch&& launch) {
+  if (plants.n == 0) {
+    launch();
+  } else {
+    launch(plants);
+  }
+}
+
+template <class Tile>
+void launch_check(int blocks, uint32_t seed, int rounds, int scaled, unsigned* cu_tiles, unsigned* cu_bad, CheckPlants plants) {
+  with_plants(plants, [&](auto... pl) {
+    hipLaunchKernelGGL((mfma_check<Tile, decltype(pl)...>), dim3(blocks), dim3(kBlock), 0, nullptr, seed, rounds, scaled, cu_tiles,
+                       cu_bad, pl...);
+  });
+}
+
 template <class Tile, bool kTimed>
 void launch_rate(int blocks, uint32_t seed, int iters, unsigned* fails, unsigned long long* xt, unsigned* xw, RatePlants plants) {
-  if (plants.n == 0) {
-    hipLaunchKernelGGL((mfma_throughput<Tile, kTimed>), dim3(blocks), dim3(kBlock), 0, nullptr, seed, iters, fails, xt, xw);
-  } else {
-    hipLaunchKernelGGL((mfma_throughput<Tile, kTimed, RatePlants>), dim3(blocks), dim3(kBlock), 0, nullptr, seed, iters, fails,
-                       xt, xw, plants);
-  }
+  with_plants(plants, [&](auto... pl) {
+    hipLaunchKernelGGL((mfma_throughput<Tile, kTimed, decltype(pl)...>), dim3(blocks), dim3(kBlock), 0, nullptr, seed, iters, fails,
+                       xt, xw, pl...);
+  });
 }
 
 // one throughput launch of a burn dtype: bf16 (timed per XCC into xt / xw) or MX fp8 / fp4
@@ -404,42 +391,113 @@ bool rate_plant_ok(const bgc_mfma_rate_plant& p) {
   return p.wave >= 0 && p.lane >= 0 && p.lane < 64 && p.chain >= 0 && p.chain < 4 && p.i >= 0 && p.i < 4;
 }
 
-// plants in device memory; none allocates nothing
-template <class P>
-int upload_plants(DeviceBuffer& d, const std::vector<P>& plants) {
-  if (plants.empty()) return 0;
-  HIP_TRY(d.alloc(plants.size() * sizeof(P)));
-  HIP_TRY(hipMemcpy(d.p, plants.data(), plants.size() * sizeof(P), hipMemcpyHostToDevice));
-  return 0;
+// (launch, place in it) of a test plant: an MX plant names its check variant or rate format, the
+// bf16 run has one launch of each kind.
+std::pair<int, bgc_mfma_check_plant> split(const bgc_mfma_check_plant& p) { return {0, p}; }
+std::pair<int, bgc_mfma_rate_plant> split(const bgc_mfma_rate_plant& p) { return {0, p}; }
+std::pair<int, bgc_mfma_check_plant> split(const bgc_lowp_check_plant& p) { return {p.variant, p.at}; }
+std::pair<int, bgc_mfma_rate_plant> split(const bgc_lowp_rate_plant& p) { return {p.fmt, p.at}; }
+
+// The check-phase or the rate-phase plants of one run, sorted by the launch they belong to.
+template <class At>
+struct HostPlants {
+  std::vector<At> host[4];
+  DeviceBuffer dev[4];
+  // Before the device is touched: false unless the list, every plant's launch (< launches) and its place (ok) are valid.
+  template <class P, class Ok>
+  bool take(const P* plants, int n, int launches, Ok&& ok) {
+    if (!plant_list_ok(plants, n)) return false;
+    for (int j = 0; j < n; ++j) {
+      const auto [launch, at] = split(plants[j]);
+      if (launch < 0 || launch >= launches || !ok(at)) return false;
+      host[launch].push_back(at);
+    }
+    return true;
+  }
+  // Once the launch size is known: refuse a plant in a wave beyond it, then copy each launch's plants to
+  // the device (a launch without plants allocates nothing).
+  int upload(int blocks) {
+    for (int l = 0; l < 4; ++l) {
+      for (const At& p : host[l]) {
+        if (p.wave >= blocks * (kBlock / 64)) {
+          g_last_error = "invalid arguments: plant in a wave beyond the launch";
+          return 1;
+        }
+      }
+      if (host[l].empty()) continue;
+      HIP_TRY(dev[l].alloc(host[l].size() * sizeof(At)));
+      HIP_TRY(hipMemcpy(dev[l].p, host[l].data(), host[l].size() * sizeof(At), hipMemcpyHostToDevice));
+    }
+    return 0;
+  }
+  PlantList<At> of(int launch) const { return {dev[launch].template as<const At>(), static_cast<int>(host[launch].size())}; }
+};
+
+// Per-CU bins of a run's kLaunches check launches: tiles checked and wrong elements by cu_key(),
+// one slice of BGC_DIAG_MAX_CU_KEYS per launch.
+template <int kLaunches>
+struct CuBins {
+  static constexpr size_t kWords = static_cast<size_t>(kLaunches) * BGC_DIAG_MAX_CU_KEYS;
+  DeviceBuffer tiles, bad;
+  int alloc() {
+    HIP_TRY(tiles.alloc(kWords * sizeof(unsigned), true));
+    HIP_TRY(bad.alloc(kWords * sizeof(unsigned), true));
+    return 0;
+  }
+  unsigned* tiles_of(int launch) const { return tiles.as<unsigned>() + static_cast<size_t>(launch) * BGC_DIAG_MAX_CU_KEYS; }
+  unsigned* bad_of(int launch) const { return bad.as<unsigned>() + static_cast<size_t>(launch) * BGC_DIAG_MAX_CU_KEYS; }
+  // Download and fold: the result's tiles_checked, cus_seen, bad_cus (a CU that is bad in several launches
+  // counts once) and first 64 bad_cu_keys, each launch's wrong elements, and the XCCs that ran a check.
+  template <class Result>
+  int fold(Result* out, uint64_t* const (&mismatches)[kLaunches], unsigned* xcc_mask = nullptr) const {
+    std::vector<unsigned> h_tiles(kWords), h_bad(kWords);
+    HIP_TRY(hipMemcpy(h_tiles.data(), tiles.p, kWords * sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_bad.data(), bad.p, kWords * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (int k = 0; k < BGC_DIAG_MAX_CU_KEYS; ++k) {
+      bool seen = false, bad_here = false;
+      for (int l = 0; l < kLaunches; ++l) {
+        const size_t i = static_cast<size_t>(l) * BGC_DIAG_MAX_CU_KEYS + static_cast<size_t>(k);
+        seen = seen || h_tiles[i];
+        bad_here = bad_here || h_bad[i];
+        out->tiles_checked += h_tiles[i];
+        *mismatches[l] += h_bad[i];
+      }
+      if (!seen) continue;
+      out->cus_seen++;
+      if (xcc_mask) *xcc_mask |= 1u << ((k >> 8) & 7);
+      if (bad_here) {
+        if (out->bad_cus < 64) out->bad_cu_keys[out->bad_cus] = k;
+        out->bad_cus++;
+      }
+    }
+    return 0;
+  }
+};
+
+// FLOPs of one throughput launch: 4 chains of 16x16xkK MFMAs per wave and iteration
+template <class Tile>
+double rate_flops(int blocks, int iters) {
+  return static_cast<double>(blocks) * (kBlock / 64) * iters * 4.0 * (2.0 * 16 * 16 * Tile::kK);
 }
 
 int mfma_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_mfma_check_plant* check, int n_check,
              const bgc_mfma_rate_plant* rate, int n_rate, bgc_mfma_result* out) {
   const int rounds = BGC_MFMA_CHECK_ROUNDS;
-  bool ok = out && waves_per_cu > 0 && throughput_iters > 0 && throughput_iters <= (1 << 18) && plant_list_ok(check, n_check) &&
-            plant_list_ok(rate, n_rate);
-  for (int j = 0; ok && j < n_check; ++j) ok = check_plant_ok(check[j], rounds);
-  for (int j = 0; ok && j < n_rate; ++j) ok = rate_plant_ok(rate[j]);
-  if (!ok) {
+  HostPlants<bgc_mfma_check_plant> check_plants;
+  HostPlants<bgc_mfma_rate_plant> rate_plants;
+  if (!(out && waves_per_cu > 0 && throughput_iters > 0 && throughput_iters <= (1 << 18) &&
+        check_plants.take(check, n_check, 1, [&](const auto& at) { return check_plant_ok(at, rounds); }) &&
+        rate_plants.take(rate, n_rate, 1, rate_plant_ok))) {
     g_last_error = "invalid arguments";
     return 1;
   }
   std::memset(out, 0, sizeof(*out));
   HIP_TRY(hipSetDevice(device));
   const int blocks = wave_blocks(device, waves_per_cu);
-  const std::vector<bgc_mfma_check_plant> h_check(check, check + n_check);
-  const std::vector<bgc_mfma_rate_plant> h_rate(rate, rate + n_rate);
-  for (const auto& p : h_check) ok = ok && p.wave < blocks * (kBlock / 64);
-  for (const auto& p : h_rate) ok = ok && p.wave < blocks * (kBlock / 64);
-  if (!ok) {
-    g_last_error = "invalid arguments: plant in a wave beyond the launch";
-    return 1;
-  }
-  DeviceBuffer d_check, d_rate;
-  if (upload_plants(d_check, h_check) != 0 || upload_plants(d_rate, h_rate) != 0) return 1;
-  DeviceBuffer tiles, bad, fails, xticks, xwaves;
-  HIP_TRY(tiles.alloc(BGC_DIAG_MAX_CU_KEYS * sizeof(unsigned), true));
-  HIP_TRY(bad.alloc(BGC_DIAG_MAX_CU_KEYS * sizeof(unsigned), true));
+  if (check_plants.upload(blocks) != 0 || rate_plants.upload(blocks) != 0) return 1;
+  CuBins<1> bins;
+  if (bins.alloc() != 0) return 1;
+  DeviceBuffer fails, xticks, xwaves;
   HIP_TRY(fails.alloc(sizeof(unsigned)));
   HIP_TRY(xticks.alloc(8 * sizeof(unsigned long long)));
   HIP_TRY(xwaves.alloc(8 * sizeof(unsigned)));
@@ -447,13 +505,7 @@ int mfma_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, 
   HIP_TRY(ev.create());
   float ms_check = 0.f, ms_tp = 0.f;
   if (timed(ev, &ms_check, [&] {
-        if (n_check == 0) {
-          hipLaunchKernelGGL(mfma_check<>, dim3(blocks), dim3(kBlock), 0, nullptr, seed, rounds, tiles.as<unsigned>(),
-                             bad.as<unsigned>());
-        } else {
-          hipLaunchKernelGGL(mfma_check<CheckPlants>, dim3(blocks), dim3(kBlock), 0, nullptr, seed, rounds, tiles.as<unsigned>(),
-                             bad.as<unsigned>(), CheckPlants{d_check.as<const bgc_mfma_check_plant>(), n_check});
-        }
+        launch_check<Bf16Tile>(blocks, seed, rounds, 0, bins.tiles_of(0), bins.bad_of(0), check_plants.of(0));
       }) != 0) {
     return 1;
   }
@@ -464,14 +516,12 @@ int mfma_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, 
   HIP_TRY(hipMemset(fails.p, 0, sizeof(unsigned)));
   HIP_TRY(hipMemset(xticks.p, 0, 8 * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(xwaves.p, 0, 8 * sizeof(unsigned)));
-  const RatePlants rate_plants{d_rate.as<const bgc_mfma_rate_plant>(), n_rate};
-  if (timed(ev, &ms_tp, [&] { launch_throughput(BGC_BURN_BF16, blocks, seed, throughput_iters, fails.as<unsigned>(), xt, xw, rate_plants); }) != 0) {
+  if (timed(ev, &ms_tp, [&] {
+        launch_throughput(BGC_BURN_BF16, blocks, seed, throughput_iters, fails.as<unsigned>(), xt, xw, rate_plants.of(0));
+      }) != 0) {
     return 1;
   }
-  std::vector<unsigned> h_tiles(BGC_DIAG_MAX_CU_KEYS), h_bad(BGC_DIAG_MAX_CU_KEYS);
   unsigned h_fails = 0;
-  HIP_TRY(hipMemcpy(h_tiles.data(), tiles.p, h_tiles.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h_bad.data(), bad.p, h_bad.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(&h_fails, fails.p, sizeof(unsigned), hipMemcpyDeviceToHost));
   unsigned long long h_ticks[8];
   unsigned h_waves[8];
@@ -490,22 +540,10 @@ int mfma_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, 
     hi = std::max(hi, out->xcc_wave_us[x]);
   }
   out->xcc_balance = hi > 0 ? lo / hi : 0.0;
-  bool xcc_seen[8] = {false};
-  for (int k = 0; k < BGC_DIAG_MAX_CU_KEYS; ++k) {
-    if (!h_tiles[static_cast<size_t>(k)]) continue;
-    out->cus_seen++;
-    out->tiles_checked += h_tiles[static_cast<size_t>(k)];
-    xcc_seen[(k >> 8) & 7] = true;
-    if (h_bad[static_cast<size_t>(k)]) {
-      out->mismatches += h_bad[static_cast<size_t>(k)];
-      if (out->bad_cus < 64) out->bad_cu_keys[out->bad_cus] = k;
-      out->bad_cus++;
-    }
-  }
-  for (bool s : xcc_seen) out->xccs_seen += s ? 1 : 0;
-  const double waves = static_cast<double>(blocks) * (kBlock / 64);
-  const double flops = waves * throughput_iters * 4.0 * (2.0 * 16 * 16 * Bf16Tile::kK);
-  out->tflops = flops / (ms_tp * 1e-3) / 1e12;
+  unsigned xcc_mask = 0;
+  if (bins.fold(out, {&out->mismatches}, &xcc_mask) != 0) return 1;
+  out->xccs_seen = __builtin_popcount(xcc_mask);
+  out->tflops = rate_flops<Bf16Tile>(blocks, throughput_iters) / (ms_tp * 1e-3) / 1e12;
   out->throughput_ok = h_fails == 0;
   out->elapsed_ms = ms_check + ms_tp;
   return 0;
@@ -514,66 +552,31 @@ int mfma_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, 
 int lowp_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_lowp_check_plant* check, int n_check,
              const bgc_lowp_rate_plant* rate, int n_rate, bgc_lowp_result* out) {
   const int rounds = BGC_LOWP_CHECK_ROUNDS;
-  bool ok = out && waves_per_cu > 0 && waves_per_cu <= 64 && throughput_iters > 0 && throughput_iters <= (1 << 16) &&
-            plant_list_ok(check, n_check) && plant_list_ok(rate, n_rate);
-  for (int j = 0; ok && j < n_check; ++j) ok = check[j].variant >= 0 && check[j].variant < 4 && check_plant_ok(check[j].at, rounds);
-  for (int j = 0; ok && j < n_rate; ++j) ok = (rate[j].fmt == 0 || rate[j].fmt == 1) && rate_plant_ok(rate[j].at);
-  if (!ok) {
+  // launches: check variant (0 fp8, 1 fp8 scaled, 2 fp4, 3 fp4 scaled), rate format (0 fp8, 1 fp4)
+  HostPlants<bgc_mfma_check_plant> check_plants;
+  HostPlants<bgc_mfma_rate_plant> rate_plants;
+  if (!(out && waves_per_cu > 0 && waves_per_cu <= 64 && throughput_iters > 0 && throughput_iters <= (1 << 16) &&
+        check_plants.take(check, n_check, 4, [&](const auto& at) { return check_plant_ok(at, rounds); }) &&
+        rate_plants.take(rate, n_rate, 2, rate_plant_ok))) {
     g_last_error = "invalid arguments";
     return 1;
   }
   std::memset(out, 0, sizeof(*out));
   HIP_TRY(hipSetDevice(device));
   const int blocks = wave_blocks(device, waves_per_cu);
-  // test plants, sorted by the launch they belong to: check variant [fmt][scaled], rate format
-  std::vector<bgc_mfma_check_plant> h_check[4];
-  std::vector<bgc_mfma_rate_plant> h_rate[2];
-  for (int j = 0; j < n_check; ++j) {
-    ok = ok && check[j].at.wave < blocks * (kBlock / 64);
-    h_check[check[j].variant].push_back(check[j].at);
-  }
-  for (int j = 0; j < n_rate; ++j) {
-    ok = ok && rate[j].at.wave < blocks * (kBlock / 64);
-    h_rate[rate[j].fmt].push_back(rate[j].at);
-  }
-  if (!ok) {
-    g_last_error = "invalid arguments: plant in a wave beyond the launch";
-    return 1;
-  }
-  DeviceBuffer d_check[4], d_rate[2];
-  for (int v = 0; v < 4; ++v) {
-    if (upload_plants(d_check[v], h_check[v]) != 0) return 1;
-  }
-  for (int i = 0; i < 2; ++i) {
-    if (upload_plants(d_rate[i], h_rate[i]) != 0) return 1;
-  }
-  auto launch_check = [&](auto fmt, int sc, unsigned* tiles_v, unsigned* bad_v) {
-    constexpr int kFmt = decltype(fmt)::value;
-    const int v = (kFmt == 0 ? 0 : 2) + sc;
-    if (h_check[v].empty()) {
-      hipLaunchKernelGGL(mfma_lowp_check<kFmt>, dim3(blocks), dim3(kBlock), 0, nullptr, seed, rounds, sc, tiles_v, bad_v);
-    } else {
-      hipLaunchKernelGGL((mfma_lowp_check<kFmt, CheckPlants>), dim3(blocks), dim3(kBlock), 0, nullptr, seed, rounds, sc, tiles_v, bad_v,
-                         CheckPlants{d_check[v].as<const bgc_mfma_check_plant>(), static_cast<int>(h_check[v].size())});
-    }
-  };
-  // bins: [fmt][scaled] tiles and mismatches per CU key
-  DeviceBuffer tiles, bad, fails;
-  const size_t bins = 4 * static_cast<size_t>(BGC_DIAG_MAX_CU_KEYS);
-  HIP_TRY(tiles.alloc(bins * sizeof(unsigned), true));
-  HIP_TRY(bad.alloc(bins * sizeof(unsigned), true));
+  if (check_plants.upload(blocks) != 0 || rate_plants.upload(blocks) != 0) return 1;
+  CuBins<4> bins;  // by check variant
+  if (bins.alloc() != 0) return 1;
+  DeviceBuffer fails;
   HIP_TRY(fails.alloc(2 * sizeof(unsigned)));
-  auto* t = tiles.as<unsigned>();
-  auto* b = bad.as<unsigned>();
   auto* f = fails.as<unsigned>();
   Events ev;
   HIP_TRY(ev.create());
   float total = 0.f;
   if (timed(ev, &total, [&] {
         for (int sc = 0; sc < 2; ++sc) {
-          const size_t o8 = static_cast<size_t>(sc) * BGC_DIAG_MAX_CU_KEYS, o4 = (2 + static_cast<size_t>(sc)) * BGC_DIAG_MAX_CU_KEYS;
-          launch_check(std::integral_constant<int, 0>{}, sc, t + o8, b + o8);
-          launch_check(std::integral_constant<int, 4>{}, sc, t + o4, b + o4);
+          launch_check<MxTile<0>>(blocks, seed, rounds, sc, bins.tiles_of(sc), bins.bad_of(sc), check_plants.of(sc));
+          launch_check<MxTile<4>>(blocks, seed, rounds, sc, bins.tiles_of(2 + sc), bins.bad_of(2 + sc), check_plants.of(2 + sc));
         }
       }) != 0) {
     return 1;
@@ -583,39 +586,19 @@ int lowp_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, 
   HIP_TRY(hipMemset(f, 0, 2 * sizeof(unsigned)));
   float ms_fmt[2] = {0.f, 0.f};
   for (int i = 0; i < 2; ++i) {
-    const RatePlants rate_plants{d_rate[i].as<const bgc_mfma_rate_plant>(), static_cast<int>(h_rate[i].size())};
     if (timed(ev, &ms_fmt[i], [&] {
-          launch_throughput(i == 0 ? BGC_BURN_FP8 : BGC_BURN_FP4, blocks, seed, throughput_iters, f + i, nullptr, nullptr, rate_plants);
+          launch_throughput(i == 0 ? BGC_BURN_FP8 : BGC_BURN_FP4, blocks, seed, throughput_iters, f + i, nullptr, nullptr, rate_plants.of(i));
         }) != 0) {
       return 1;
     }
     total += ms_fmt[i];
   }
-  std::vector<unsigned> h_t(bins), h_b(bins);
   unsigned h_f[2] = {0, 0};
-  HIP_TRY(hipMemcpy(h_t.data(), t, bins * sizeof(unsigned), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h_b.data(), b, bins * sizeof(unsigned), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(h_f, f, sizeof(h_f), hipMemcpyDeviceToHost));
-  uint64_t* mism[4] = {&out->fp8_mismatches, &out->fp8_scaled_mismatches, &out->fp4_mismatches,
-                       &out->fp4_scaled_mismatches};
-  for (int k = 0; k < BGC_DIAG_MAX_CU_KEYS; ++k) {
-    unsigned seen = 0, bad_here = 0;
-    for (int v = 0; v < 4; ++v) {
-      const size_t i = static_cast<size_t>(v) * BGC_DIAG_MAX_CU_KEYS + static_cast<size_t>(k);
-      seen += h_t[i];
-      bad_here += h_b[i];
-      *mism[v] += h_b[i];
-      out->tiles_checked += h_t[i];
-    }
-    if (!seen) continue;
-    out->cus_seen++;
-    if (bad_here) {
-      if (out->bad_cus < 64) out->bad_cu_keys[out->bad_cus] = k;
-      out->bad_cus++;
-    }
+  if (bins.fold(out, {&out->fp8_mismatches, &out->fp8_scaled_mismatches, &out->fp4_mismatches, &out->fp4_scaled_mismatches}) != 0) {
+    return 1;
   }
-  const double waves = static_cast<double>(blocks) * (kBlock / 64);
-  const double flops = waves * throughput_iters * 4.0 * (2.0 * 16 * 16 * MxTile<0>::kK);
+  const double flops = rate_flops<MxTile<0>>(blocks, throughput_iters);  // the same for fp4
   out->fp8_tflops = ms_fmt[0] > 0 ? flops / (ms_fmt[0] * 1e-3) / 1e12 : 0.0;
   out->fp4_tflops = ms_fmt[1] > 0 ? flops / (ms_fmt[1] * 1e-3) / 1e12 : 0.0;
   out->throughput_ok = h_f[0] == 0 && h_f[1] == 0;
@@ -667,8 +650,7 @@ int bgc_diag_burn_dtype(int device, int duration_ms, int waves_per_cu, uint32_t 
   HIP_TRY(total.create());
   // size one launch to ~10 ms at MI355X rates (iters * 4 MFMA per wave), measured below
   int iters = 2048;
-  const double mfma_k = dtype == BGC_BURN_BF16 ? Bf16Tile::kK : MxTile<0>::kK;
-  const double flops_per_iter = static_cast<double>(blocks) * (kBlock / 64) * 4.0 * (2.0 * 16 * 16 * mfma_k);
+  const double flops_per_iter = dtype == BGC_BURN_BF16 ? rate_flops<Bf16Tile>(blocks, 1) : rate_flops<MxTile<0>>(blocks, 1);
   float ms = 0.f;
   HIP_TRY(hipEventRecord(total.a, nullptr));
   double sum_flops = 0;

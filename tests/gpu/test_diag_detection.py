@@ -295,6 +295,24 @@ def test_mfma_lowp_check_counts_planted_accumulators(edge, variant):
     _check_cu_keys(r)
 
 
+def test_mfma_lowp_plant_in_every_wave_of_two_variants():
+    """Every wave reports one mismatch in the first and in the last variant's bins, so every CU is
+    bad in both and is still counted once; the 64-entry key array beyond its capacity."""
+    from bacchus_gpu_controller_amd import ops
+
+    waves = _waves(4)
+    plants = [("fp8", ops.ALL_WAVES, 1, 33, 1, 4.0), ("fp4_scaled", ops.ALL_WAVES, 0, 2, 3, -2.0)]
+    r = ops.mfma_lowp_planted(plants, waves_per_cu=4, iters=RATE_ITERS)
+    assert r["fp8_mismatches"] == r["fp4_scaled_mismatches"] == waves, r
+    assert r["fp8_scaled_mismatches"] == r["fp4_mismatches"] == 0, r
+    assert r["mismatches"] == 2 * waves, r
+    assert r["tiles_checked"] == 4 * waves * LOWP_ROUNDS, r
+    assert r["bad_cus"] == r["cus_seen"], r
+    assert len(r["bad_cu_keys"]) == 64, r
+    assert r["throughput_ok"] is True, r
+    _check_cu_keys(r)
+
+
 @pytest.mark.parametrize("fmt", ["fp8", "fp4"])
 def test_mfma_lowp_rate_phase_plant_clears_throughput_ok(fmt):
     from bacchus_gpu_controller_amd import ops
