@@ -26,6 +26,8 @@ These are the only compute kernels in the framework: the reference controller ha
 * ``hbm_planted``, ``hbm_walk_planted``, ``pcie_planted``, ``mfma_planted``,
   ``mfma_lowp_planted``, ``gemm_soak_planted`` — for tests: the same diagnostics with wrong
   values planted in their own data, to show that they are detected (see below)
+* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile`` — for tests:
+  the same diagnostics, returning the data they generated for themselves (see below)
 
 All fail loudly (RuntimeError) if ``libbgc_gpu_diag.so`` or the GPU is missing; there
 is no CPU fallback.
@@ -135,6 +137,49 @@ def gemm_soak_planted(m, n, k, launches, plants, device=0, seed=0x5EED):
     """`plants` = [(launch, row, col, delta), ...] add delta to C[row][col] after that launch and
     before its checksums; only the first and the last launch are checked."""
     return json.loads(native().diag_gemm_soak_planted(device, m, n, k, launches, seed, list(plants)))
+
+
+# ---------------------------------------------------------------------------------------------
+# Generated data, for tests only: the same diagnostics, returning the data they generated for
+# themselves (gpu_diag.h documents every pattern) next to their result, so a test can compare it
+# with an independent reference.  At most 128 MiB come back from one call.
+
+TILE_PATHS = {"bf16": 0, "fp8": 1, "fp4": 2}
+TILE_LANE = np.dtype([("a", "<u4", 8), ("b", "<u4", 8), ("ea", "<i4"), ("eb", "<i4"), ("acc", "<f4", 4), ("expect", "<f4", 4)])
+
+
+def hbm_data(nbytes, iters, device=0, seed=0x5EED):
+    """(result, the copy buffer after the last of `iters` iterations as uint32 words)"""
+    r, data = native().diag_hbm_data(device, nbytes, iters, seed)
+    return json.loads(r), np.frombuffer(data, dtype="<u4")
+
+
+def hbm_walk_data(nbytes, chunk_bytes, passes, device=0, seed=0x5EED):
+    """(result with ``chunk_list``, the chunks' contents after `passes` passes, back to back, as
+    uint64 words)"""
+    r, data = native().diag_hbm_walk_data(device, nbytes, chunk_bytes, passes, seed)
+    return json.loads(r), np.frombuffer(data, dtype="<u8")
+
+
+def pcie_data(nbytes, device=0, seed=0x5EED):
+    """(result, the host buffer after the round trip as uint64 words)"""
+    r, data = native().diag_pcie_data(device, nbytes, seed)
+    return json.loads(r), np.frombuffer(data, dtype="<u8")
+
+
+def gemm_soak_data(m, n, k, device=0, seed=0x5EED):
+    """(result, A m x k and Bt n x k as bf16 bit patterns, rref m and cref n as int64, C m x n fp32)
+    of one launch"""
+    r, a, bt, rref, cref, c = native().diag_gemm_soak_data(device, m, n, k, seed)
+    return (json.loads(r), np.frombuffer(a, dtype="<u2").reshape(m, k), np.frombuffer(bt, dtype="<u2").reshape(n, k),
+            np.frombuffer(rref, dtype="<i8"), np.frombuffer(cref, dtype="<i8"), np.frombuffer(c, dtype="<f4").reshape(m, n))
+
+
+def mfma_tile(path, tile, scaled=False, device=0, seed=0x5EED):
+    """What each of the 64 lanes holds for tile `tile` of the "bf16", "fp8" or "fp4" check: a
+    record array of TILE_LANE (fragment dwords a and b, scale exponents ea and eb, the matrix
+    core's acc and the check's expect)."""
+    return np.frombuffer(native().diag_mfma_tile(device, TILE_PATHS[path], int(scaled), seed, tile), dtype=TILE_LANE)
 
 
 def _bf16_bytes(x):

@@ -367,9 +367,10 @@ bool soak_shape_ok(int m, int n, int k) {
          n <= 32768 && k <= 32768;
 }
 
-// bgc_diag_gemm_soak, and bgc_diag_gemm_soak_planted with its test plants added to C after their launch
+// bgc_diag_gemm_soak, bgc_diag_gemm_soak_planted with its test plants added to C after their launch, and
+// bgc_diag_gemm_soak_data with the operands, the reference checksums and C downloaded to `dump` at the end
 int soak_run(int device, int m, int n, int k, int launches, uint32_t seed, const bgc_soak_plant* plants, int n_plants,
-             bgc_soak_result* out) {
+             const bgc_soak_data* dump, bgc_soak_result* out) {
   bool ok = out && launches > 0 && soak_shape_ok(m, n, k) && plant_list_ok(plants, n_plants);
   for (int j = 0; ok && j < n_plants; ++j) {
     const bgc_soak_plant& p = plants[j];
@@ -452,6 +453,13 @@ int soak_run(int device, int m, int n, int k, int launches, uint32_t seed, const
     if (it == 0 && verify(&out->row_mismatches, &out->col_mismatches) != 0) return 1;
   }
   if (launches > 1 && verify(&out->row_mismatches, &out->col_mismatches) != 0) return 1;
+  if (dump) {
+    HIP_TRY(hipMemcpy(dump->a, a.p, na * 2, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dump->bt, bt.p, nb * 2, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dump->c, c.p, nc * 4, hipMemcpyDeviceToHost));
+    std::memcpy(dump->rref, rr.data(), rr.size() * 8);
+    std::memcpy(dump->cref, cr.data(), cr.size() * 8);
+  }
   out->m = m;
   out->n = n;
   out->k = k;
@@ -469,12 +477,23 @@ int soak_run(int device, int m, int n, int k, int launches, uint32_t seed, const
 extern "C" {
 
 int bgc_diag_gemm_soak(int device, int m, int n, int k, int launches, uint32_t seed, bgc_soak_result* out) {
-  return soak_run(device, m, n, k, launches, seed, nullptr, 0, out);
+  return soak_run(device, m, n, k, launches, seed, nullptr, 0, nullptr, out);
 }
 
 int bgc_diag_gemm_soak_planted(int device, int m, int n, int k, int launches, uint32_t seed, const bgc_soak_plant* plants,
                                int n_plants, bgc_soak_result* out) {
-  return soak_run(device, m, n, k, launches, seed, plants, n_plants, out);
+  return soak_run(device, m, n, k, launches, seed, plants, n_plants, nullptr, out);
+}
+
+int bgc_diag_gemm_soak_data(int device, int m, int n, int k, uint32_t seed, const bgc_soak_data* data, bgc_soak_result* out) {
+  // of a valid shape (each side <= 32768, so no product overflows): operands, C and the checksums
+  const auto bytes = [&] { return 2ULL * m * k + 2ULL * n * k + 4ULL * m * n + 8ULL * m + 8ULL * n; };
+  if (!data || !data->a || !data->bt || !data->rref || !data->cref || !data->c ||
+      (soak_shape_ok(m, n, k) && bytes() > BGC_DIAG_MAX_DATA_BYTES)) {
+    g_last_error = "invalid arguments: five destinations, and at most 128 MiB to return";
+    return 1;
+  }
+  return soak_run(device, m, n, k, 1, seed, nullptr, 0, data, out);
 }
 
 int bgc_diag_gemm_tiled(int device, int m, int n, int k, const uint16_t* a_bf16, const uint16_t* bt_bf16, float* c) {

@@ -15,8 +15,48 @@
 extern "C" {
 #endif
 
-#define BGC_DIAG_ABI_VERSION 12
+#define BGC_DIAG_ABI_VERSION 13
 #define BGC_DIAG_MAX_CU_KEYS 2048
+
+// The data the diagnostics generate for themselves.  All arithmetic is modulo 2^32 (mix32) or
+// 2^64 (mix64); u32(x) is the low 32 bits of x.
+//
+//   mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+//   mix64(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33
+//   trit(h):  (h mod 3) - 1, a value in {-1, 0, 1}
+//
+//  * HBM stream (bgc_diag_hbm).  A buffer is 16-byte elements i = 0.. of four 32-bit words each.
+//    With pattern seed s, word c (0..3) of element i is mix32((w + c) ^ s) where
+//    w = u32(4 i) ^ (u32(i >> 30) * 0x9e3779b9).  Timed iteration `it` (0-based) fills, copies and
+//    checks with s = mix32(seed + (it + 1) * 0x9e3779b9); the untimed warm-up fill uses
+//    s = mix32(seed).  The seeds of one run are pairwise distinct, so every word of an iteration's
+//    pattern differs from the same word of any other iteration's and of the warm-up's: a fill or a
+//    copy that wrote nothing cannot pass on what was there before.  Both buffers are set to 0xFF
+//    bytes once after allocation.
+//  * HBM walk (bgc_diag_hbm_walk).  key = mix64(0x9e3779b97f4a7c15 ^ seed).  In the first pass the
+//    64-bit word at device address a holds a ^ key, in the second a ^ ~key.
+//  * PCIe (bgc_diag_pcie).  64-bit word i of the transfer is mix32(u32(i) ^ seed) << 32 |
+//    mix32(u32(i) ^ ~seed).  A transfer is at most 16 GiB, so u32(i) is all of i and both halves
+//    take a different value in every word.
+//  * GEMM soak (bgc_diag_gemm_soak).  Element i (row-major) of an operand with operand seed s is
+//    trit(mix32(u32(i) ^ mix32(u32(i >> 32) + s))) as bf16; A[m][k] uses s = seed, Bt[n][k] (B
+//    transposed) s = seed ^ 0xB7B7B7B7.  The reference checksums are rref = A (B 1), the row sums
+//    of C, and cref = (1^T A) B, its column sums.
+//  * Matrix-core tiles (bgc_diag_mfma, bgc_diag_mfma_lowp, bgc_diag_burn_dtype).
+//    op(s, tile, r, c, which) = trit(mix32(s ^ mix32(tile * 0x9e3779b9 + which) ^ u32(128 r + c))).
+//    bf16 tile (16x16x32): A[row][k] = op(seed, tile, row, k, 0xA), B[k][col] = op(seed, tile, k, col, 0xB),
+//    as bf16 values.  MX tile (16x16x128): A[row][k] = op(seed, tile, row, c(k), 0xA), B[k][col] =
+//    op(seed, tile, col, c(k), 0xB), as e4m3 codes 0x38 / 0x00 / 0xB8 or e2m1 codes 0x2 / 0x0 / 0xA for
+//    1 / 0 / -1.  c(k) numbers the elements in the order the lanes hold them (below): fp4, c(k) = k;
+//    fp8, c(k) = 32 ((k mod 64) / 16) + 16 (k / 64) + k mod 16.  Scale exponents (E8M0 byte 127 + e)
+//    of the K-block blk = k / 32: ea[row][blk] = op(seed ^ 0x5ca1e, tile, row, blk, 0xA), eb[col][blk] =
+//    op(seed ^ 0x5ca1e, tile, col, blk, 0xB) in the scaled variants, 0 otherwise.  The exact result is
+//    C[row][col] = sum_blk 2^(ea[row][blk] + eb[col][blk]) sum_{k in blk} A[row][k] B[k][col].  A check
+//    wave w takes tiles w * rounds .. w * rounds + rounds - 1, a throughput wave w tile w.
+//    Lane l = 16 g + rc of the wave holds, of A row rc and of B column rc: bf16, k = 8 g + j in
+//    element j of 8; fp8, K 16 g .. 16 g + 15 in bytes 0..15 and K 64 + 16 g .. in bytes 16..31; fp4,
+//    K 32 g .. 32 g + 31 in 16 bytes, the even k in the low nibble; the scale byte of (rc, block g).
+//    The result lane l holds C[4 g + i][rc] in accumulator element i.
 
 typedef struct {
   uint64_t bytes;          // buffer size tested
@@ -245,6 +285,50 @@ typedef struct {
 } bgc_soak_plant;
 int bgc_diag_gemm_soak_planted(int device, int m, int n, int k, int launches, uint32_t seed,
                                const bgc_soak_plant* plants, int n_plants, bgc_soak_result* out);
+
+// ---------------------------------------------------------------------------------------------
+// Generated data: FOR TESTS ONLY, never loaded by the node agent or the diag worker.  Each runs
+// the same implementation as the entry point it is named after and then copies the data that
+// run generated ("the data the diagnostics generate", above) to host memory of the caller, so a
+// test can compare it with an independent reference.  A null destination, or a run whose copies
+// to the host exceed BGC_DIAG_MAX_DATA_BYTES in all, is refused with "invalid arguments" before
+// the device is touched.
+#define BGC_DIAG_MAX_DATA_BYTES (128ULL << 20)
+
+// bgc_diag_hbm, then the copy buffer as the last iteration left it: `bytes` rounded down to 16,
+// to `data`.
+int bgc_diag_hbm_data(int device, uint64_t bytes, int iters, uint32_t seed, void* data, bgc_hbm_result* out);
+// bgc_diag_hbm_walk_planted without plants, ended after `passes` (1 or 2) passes; then every
+// chunk's contents, in the order of `chunks` and without gaps, to `data` (`bytes` rounded down to
+// 2 MiB).  All chunks are returned: max_chunks must cover them.
+int bgc_diag_hbm_walk_data(int device, uint64_t bytes, uint64_t chunk_bytes, int passes, uint32_t seed,
+                           bgc_walk_chunk* chunks, int max_chunks, void* data, bgc_hbm_walk_result* out);
+// bgc_diag_pcie with one iteration; the host buffer that the round-trip check compared with the
+// pattern (`bytes` rounded down to 8) to `data`.
+int bgc_diag_pcie_data(int device, uint64_t bytes, uint32_t seed, void* data, bgc_pcie_result* out);
+typedef struct {
+  uint16_t* a;    // m x k bf16 bit patterns
+  uint16_t* bt;   // n x k
+  int64_t* rref;  // m reference row checksums
+  int64_t* cref;  // n reference column checksums
+  float* c;       // m x n, after the launch
+} bgc_soak_data;
+// bgc_diag_gemm_soak with one launch; all five destinations are required.
+int bgc_diag_gemm_soak_data(int device, int m, int n, int k, uint32_t seed, const bgc_soak_data* data,
+                            bgc_soak_result* out);
+#define BGC_TILE_BF16 0
+#define BGC_TILE_FP8 1
+#define BGC_TILE_FP4 2
+typedef struct {
+  uint32_t a[8], b[8];  // the lane's A and B fragment as the MFMA takes it (bf16 and fp4: 4 dwords, the rest 0)
+  int32_t ea, eb;       // its scale exponents (E8M0 byte - 127)
+  float acc[4];         // what the matrix core returned
+  float expect[4];      // the check's own value of the same elements
+} bgc_tile_lane;
+// One wave runs the check's tile functions (pack, scale exponents, MFMA, expected values) on tile
+// `tile` of matrix-core path `path` (BGC_TILE_*), with block scales if `scaled` (MX paths only),
+// and every lane writes what it holds to lanes[0..63].
+int bgc_diag_mfma_tile(int device, int path, int scaled, uint32_t seed, uint32_t tile, bgc_tile_lane* lanes);
 
 // PCI bus id of a HIP device ("0000:05:00.0", lower-case hex) — the key the node agent and
 // the RCCL probe use to match a HIP device (renumbered inside a container) to amdsmi.

@@ -172,8 +172,10 @@ uint64_t mix64(uint64_t x) {
   return x;
 }
 
-// bgc_diag_hbm, and bgc_diag_hbm_planted with its test plants XORed into the copy before each check
-int hbm_run(int device, uint64_t bytes, int iters, uint32_t seed, const bgc_hbm_plant* plants, int n, bgc_hbm_result* out) {
+// bgc_diag_hbm, bgc_diag_hbm_planted with its test plants XORed into the copy before each check, and
+// bgc_diag_hbm_data with the copy downloaded to `dump` at the end
+int hbm_run(int device, uint64_t bytes, int iters, uint32_t seed, const bgc_hbm_plant* plants, int n, void* dump,
+            bgc_hbm_result* out) {
   bool ok = out && iters > 0 && bytes >= (1u << 20) && plant_list_ok(plants, n);
   bytes &= ~static_cast<uint64_t>(15);
   for (int j = 0; ok && j < n; ++j) ok = plants[j].word32_index < bytes / 4;
@@ -194,9 +196,16 @@ int hbm_run(int device, uint64_t bytes, int iters, uint32_t seed, const bgc_hbm_
   Events ev;
   HIP_TRY(ev.create());
   float best_fill = 1e30f, best_copy = 1e30f, best_check = 1e30f, total = 0.f;
-  auto fill = [&] { hipLaunchKernelGGL(hbm_fill, grid, block, 0, nullptr, a.as<u32x4>(), n16, seed); };
+  // Every fill gets a pattern seed of its own (gpu_diag.h: the warm-up is iteration -1), and both
+  // buffers start out poisoned: a fill or a copy that wrote nothing leaves data that differs from
+  // what the check expects in every word, whatever the pages or an earlier iteration held.
+  auto pattern_seed = [=](int it) { return mix32(seed + static_cast<uint32_t>(it + 1) * 0x9e3779b9U); };
+  uint32_t pseed = pattern_seed(-1);
+  HIP_TRY(hipMemset(a.p, 0xFF, bytes));
+  HIP_TRY(hipMemset(b.p, 0xFF, bytes));
+  auto fill = [&] { hipLaunchKernelGGL(hbm_fill, grid, block, 0, nullptr, a.as<u32x4>(), n16, pseed); };
   auto copy = [&] { hipLaunchKernelGGL(hbm_copy, grid, block, 0, nullptr, a.as<const u32x4>(), b.as<u32x4>(), n16); };
-  auto check = [&] { hipLaunchKernelGGL(hbm_check, grid, block, 0, nullptr, b.as<const u32x4>(), n16, seed, bad, bad + 1); };
+  auto check = [&] { hipLaunchKernelGGL(hbm_check, grid, block, 0, nullptr, b.as<const u32x4>(), n16, pseed, bad, bad + 1); };
   auto phase = [&](auto& launch, float* best) {
     float ms = 0.f;
     if (timed(ev, &ms, launch) != 0) return 1;
@@ -207,6 +216,7 @@ int hbm_run(int device, uint64_t bytes, int iters, uint32_t seed, const bgc_hbm_
   fill();  // warm-up (also first-touch of the pages)
   HIP_TRY(hipGetLastError());
   for (int it = 0; it < iters; ++it) {
+    pseed = pattern_seed(it);
     if (phase(fill, &best_fill) != 0 || phase(copy, &best_copy) != 0) return 1;
     for (int j = 0; j < n; ++j) {
       const uint32_t mask = plants[j].xor_mask;
@@ -216,6 +226,7 @@ int hbm_run(int device, uint64_t bytes, int iters, uint32_t seed, const bgc_hbm_
   }
   unsigned long long res[2];
   HIP_TRY(hipMemcpy(res, bad, sizeof(res), hipMemcpyDeviceToHost));
+  if (dump) HIP_TRY(hipMemcpy(dump, b.p, bytes, hipMemcpyDeviceToHost));
   out->bytes = bytes;
   out->iters = iters;
   out->write_gbps = static_cast<double>(bytes) / (best_fill * 1e-3) / 1e9;
@@ -233,9 +244,11 @@ constexpr uint64_t kWalkAlign = 2ULL << 20;
 // The walk over `target_bytes`, or over `fraction` of the free VRAM when that is 0 (arguments
 // checked by the callers).  Test plants are XORed in after their pass's fill; with any, the
 // allocations must come out as `target_bytes` and `chunk_bytes` imply, since the plants were
-// checked against that layout.
+// checked against that layout.  The walk ends after `passes` passes; with `dump` every chunk's
+// contents are then downloaded to it back to back, and the allocations must come out as implied too.
 int walk_run(int device, double fraction, uint64_t target_bytes, uint64_t chunk_bytes, int budget_ms, uint32_t seed,
-             const bgc_walk_plant* plants, int n, bgc_walk_chunk* chunks_out, int max_chunks, bgc_hbm_walk_result* out) {
+             const bgc_walk_plant* plants, int n, bgc_walk_chunk* chunks_out, int max_chunks, int passes, void* dump,
+             bgc_hbm_walk_result* out) {
   std::memset(out, 0, sizeof(*out));
   const auto t0 = std::chrono::steady_clock::now();
   auto elapsed_ms = [&] {
@@ -274,7 +287,7 @@ int walk_run(int device, double fraction, uint64_t target_bytes, uint64_t chunk_
   for (int c = 0; c < out->chunks && c < max_chunks; ++c) {
     chunks_out[c] = {reinterpret_cast<uint64_t>(chunks.v[static_cast<size_t>(c)].first), chunks.v[static_cast<size_t>(c)].second};
   }
-  if (n > 0 && (got != target || cb != (chunk_bytes & ~(align - 1)))) {
+  if ((n > 0 || dump) && (got != target || cb != (chunk_bytes & ~(align - 1)))) {
     g_last_error = "hbm walk: the chunks could not be allocated as the plants assume";
     return 1;
   }
@@ -284,7 +297,7 @@ int walk_run(int device, double fraction, uint64_t target_bytes, uint64_t chunk_
   HIP_TRY(ev.create());
   const uint64_t key0 = mix64(0x9e3779b97f4a7c15ULL ^ seed);
   double fill_ms = 0, check_ms = 0;
-  for (int pass = 0; pass < 2; ++pass) {
+  for (int pass = 0; pass < passes; ++pass) {
     if (pass > 0 && elapsed_ms() > budget_ms) {
       out->budget_hit = 1;
       break;
@@ -326,6 +339,13 @@ int walk_run(int device, double fraction, uint64_t target_bytes, uint64_t chunk_
     out->mismatches += res[0];
     out->passes = pass + 1;
   }
+  if (dump) {
+    char* to = static_cast<char*>(dump);
+    for (const auto& c : chunks.v) {
+      HIP_TRY(hipMemcpy(to, c.first, c.second, hipMemcpyDeviceToHost));
+      to += c.second;
+    }
+  }
   out->bytes_covered = got;
   const double moved = static_cast<double>(got) * out->passes;
   out->write_gbps = fill_ms > 0 ? moved / (fill_ms * 1e-3) / 1e9 : 0.0;
@@ -334,8 +354,10 @@ int walk_run(int device, double fraction, uint64_t target_bytes, uint64_t chunk_
   return 0;
 }
 
-// bgc_diag_pcie, and bgc_diag_pcie_planted with its test plants XORed into the uploaded buffer
-int pcie_run(int device, uint64_t bytes, int iters, uint32_t seed, const bgc_pcie_plant* plants, int n, bgc_pcie_result* out) {
+// bgc_diag_pcie, bgc_diag_pcie_planted with its test plants XORed into the uploaded buffer, and
+// bgc_diag_pcie_data with the buffer that came back copied to `dump` after the round-trip check
+int pcie_run(int device, uint64_t bytes, int iters, uint32_t seed, const bgc_pcie_plant* plants, int n, void* dump,
+             bgc_pcie_result* out) {
   bool ok = out && iters > 0 && bytes >= (1u << 20) && bytes <= (uint64_t{16} << 30) && plant_list_ok(plants, n);
   bytes &= ~static_cast<uint64_t>(7);
   const uint64_t words = bytes / 8;
@@ -354,7 +376,11 @@ int pcie_run(int device, uint64_t bytes, int iters, uint32_t seed, const bgc_pci
   HIP_TRY(d1.alloc(bytes));
   HIP_TRY(d2.alloc(bytes));
   auto* s64 = static_cast<uint64_t*>(src.p);
-  for (uint64_t i = 0; i < words; ++i) s64[i] = (static_cast<uint64_t>(mix32(static_cast<uint32_t>(i) ^ seed)) << 32) | mix32(static_cast<uint32_t>(i >> 32) + seed + 1);
+  // words <= 2^31 (16 GiB), so the low 32 bits of i are all of it: both halves differ from word to word
+  for (uint64_t i = 0; i < words; ++i) {
+    const uint32_t x = static_cast<uint32_t>(i);
+    s64[i] = (static_cast<uint64_t>(mix32(x ^ seed)) << 32) | mix32(x ^ ~seed);
+  }
   std::memset(dst.p, 0, bytes);
   std::memset(src2.p, 0x5a, bytes);
   Streams st;
@@ -376,6 +402,7 @@ int pcie_run(int device, uint64_t bytes, int iters, uint32_t seed, const bgc_pci
   const auto* d64 = static_cast<const uint64_t*>(dst.p);
   uint64_t bad = 0;
   for (uint64_t i = 0; i < words; ++i) bad += d64[i] != s64[i];
+  if (dump) std::memcpy(dump, dst.p, bytes);
   float best_h2d = 1e30f, best_d2h = 1e30f, ms = 0.f, total = 0.f;
   double best_bidir = 0;
   for (int it = 0; it < iters; ++it) {
@@ -417,11 +444,11 @@ int pcie_run(int device, uint64_t bytes, int iters, uint32_t seed, const bgc_pci
 extern "C" {
 
 int bgc_diag_hbm(int device, uint64_t bytes, int iters, uint32_t seed, bgc_hbm_result* out) {
-  return hbm_run(device, bytes, iters, seed, nullptr, 0, out);
+  return hbm_run(device, bytes, iters, seed, nullptr, 0, nullptr, out);
 }
 
 int bgc_diag_hbm_planted(int device, uint64_t bytes, uint32_t seed, const bgc_hbm_plant* plants, int n, bgc_hbm_result* out) {
-  return hbm_run(device, bytes, 1, seed, plants, n, out);
+  return hbm_run(device, bytes, 1, seed, plants, n, nullptr, out);
 }
 
 int bgc_diag_hbm_walk(int device, double fraction, uint64_t chunk_bytes, int budget_ms, uint32_t seed,
@@ -430,7 +457,7 @@ int bgc_diag_hbm_walk(int device, double fraction, uint64_t chunk_bytes, int bud
     g_last_error = "invalid arguments: 0 < fraction <= 0.99, chunk_bytes >= 64 MiB, budget_ms > 0";
     return 1;
   }
-  return walk_run(device, fraction, 0, chunk_bytes, budget_ms, seed, nullptr, 0, nullptr, 0, out);
+  return walk_run(device, fraction, 0, chunk_bytes, budget_ms, seed, nullptr, 0, nullptr, 0, 2, nullptr, out);
 }
 
 int bgc_diag_hbm_walk_planted(int device, uint64_t bytes, uint64_t chunk_bytes, uint32_t seed, const bgc_walk_plant* plants,
@@ -448,15 +475,42 @@ int bgc_diag_hbm_walk_planted(int device, uint64_t bytes, uint64_t chunk_bytes, 
     g_last_error = "invalid arguments: bytes >= 2 MiB, chunk_bytes >= 64 MiB, plants inside their chunk, pass 0 or 1";
     return 1;
   }
-  return walk_run(device, 0.0, target, chunk_bytes, INT32_MAX, seed, plants, n, chunks, max_chunks, out);
+  return walk_run(device, 0.0, target, chunk_bytes, INT32_MAX, seed, plants, n, chunks, max_chunks, 2, nullptr, out);
 }
 
 int bgc_diag_pcie(int device, uint64_t bytes, int iters, uint32_t seed, bgc_pcie_result* out) {
-  return pcie_run(device, bytes, iters, seed, nullptr, 0, out);
+  return pcie_run(device, bytes, iters, seed, nullptr, 0, nullptr, out);
 }
 
 int bgc_diag_pcie_planted(int device, uint64_t bytes, uint32_t seed, const bgc_pcie_plant* plants, int n, bgc_pcie_result* out) {
-  return pcie_run(device, bytes, 1, seed, plants, n, out);
+  return pcie_run(device, bytes, 1, seed, plants, n, nullptr, out);
+}
+
+int bgc_diag_hbm_data(int device, uint64_t bytes, int iters, uint32_t seed, void* data, bgc_hbm_result* out) {
+  if (!data || bytes > BGC_DIAG_MAX_DATA_BYTES) {
+    g_last_error = "invalid arguments";
+    return 1;
+  }
+  return hbm_run(device, bytes, iters, seed, nullptr, 0, data, out);
+}
+
+int bgc_diag_hbm_walk_data(int device, uint64_t bytes, uint64_t chunk_bytes, int passes, uint32_t seed, bgc_walk_chunk* chunks,
+                           int max_chunks, void* data, bgc_hbm_walk_result* out) {
+  const uint64_t target = bytes & ~(kWalkAlign - 1), cb = chunk_bytes & ~(kWalkAlign - 1);
+  if (!out || !data || !chunks || target == 0 || target > BGC_DIAG_MAX_DATA_BYTES || chunk_bytes < kMinChunk ||
+      (passes != 1 && passes != 2) || max_chunks < 0 || static_cast<uint64_t>(max_chunks) < (target + cb - 1) / cb) {
+    g_last_error = "invalid arguments: 2 MiB <= bytes <= 128 MiB, chunk_bytes >= 64 MiB, 1 or 2 passes, room for every chunk";
+    return 1;
+  }
+  return walk_run(device, 0.0, target, chunk_bytes, INT32_MAX, seed, nullptr, 0, chunks, max_chunks, passes, data, out);
+}
+
+int bgc_diag_pcie_data(int device, uint64_t bytes, uint32_t seed, void* data, bgc_pcie_result* out) {
+  if (!data || bytes > BGC_DIAG_MAX_DATA_BYTES) {
+    g_last_error = "invalid arguments";
+    return 1;
+  }
+  return pcie_run(device, bytes, 1, seed, nullptr, 0, data, out);
 }
 
 }  // extern "C"

@@ -16,6 +16,8 @@
 //  * On the host, bgc_diag_mfma and bgc_diag_mfma_lowp share the per-CU bins (CuBins), the test
 //    plants (HostPlants) and the choice between a kernel's production and planted instantiation
 //    (with_plants); each fills its own result struct.
+//  * bgc_diag_mfma_tile runs one round of the check in one wave (mfma_tile) and returns what every
+//    lane held, for the tests of the generated tiles.
 #include <algorithm>
 #include <cstring>
 #include <utility>
@@ -26,8 +28,12 @@ namespace {
 
 using namespace bgc_diag;
 
+// Element (r, c) of operand `which` of a tile, in {-1, 0, 1}.  Every tile trait indexes with
+// c < kOperandStride (it asserts kK <= kOperandStride), so no two (r, c) of a tile share a hash.
+constexpr int kOperandStride = 128;
+
 __device__ __forceinline__ int operand(uint32_t seed, uint32_t tile, int r, int c, uint32_t which) {
-  uint32_t h = mix32(seed ^ mix32(tile * 0x9e3779b9U + which) ^ static_cast<uint32_t>(r * 64 + c));
+  uint32_t h = mix32(seed ^ mix32(tile * 0x9e3779b9U + which) ^ static_cast<uint32_t>(r * kOperandStride + c));
   return static_cast<int>(h % 3u) - 1;
 }
 
@@ -54,6 +60,7 @@ __device__ __forceinline__ uint32_t cu_key() {
 struct Bf16Tile {
   using Frag = bf16x8;
   static constexpr int kK = 32;
+  static_assert(kK <= kOperandStride, "operand() must tell every (row, k) and (k, column) apart");
   static __device__ __forceinline__ Frag pack(uint32_t seed, uint32_t tile, int rc, int g, uint32_t which) {
     Frag v;
 #pragma unroll
@@ -111,6 +118,7 @@ template <int kFmt>
 struct MxTile {
   using Frag = i32x8;
   static constexpr int kK = 128;
+  static_assert(kK <= kOperandStride, "operand() must tell every (row or column, k) apart");
   // 32 operands of one lane (row or column `rc`, block `g`) packed for the MFMA
   static __device__ __forceinline__ Frag pack(uint32_t seed, uint32_t tile, int rc, int g, uint32_t which) {
     i32x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -218,6 +226,28 @@ __global__ __launch_bounds__(kBlock) void mfma_check(uint32_t seed, int rounds, 
     atomicAdd(&cu_tiles[key], static_cast<unsigned>(rounds));
     if (bad) atomicAdd(&cu_bad[key], bad);
   }
+}
+
+// One round of the check by one wave, for bgc_diag_mfma_tile: every lane writes out what the check
+// holds in registers (its fragments, scale exponents, accumulators and expected values).
+template <class Tile>
+__global__ __launch_bounds__(64) void mfma_tile(uint32_t seed, uint32_t tile, int scaled, bgc_tile_lane* __restrict__ lanes) {
+  const int lane = threadIdx.x, rc = lane & 15, g = lane >> 4;
+  const typename Tile::Frag a = Tile::pack(seed, tile, rc, g, 0xA);
+  const typename Tile::Frag b = Tile::pack(seed, tile, rc, g, 0xB);
+  bgc_tile_lane o = {};
+  static_assert(sizeof(a) <= sizeof(o.a), "a fragment is at most 8 dwords");
+  __builtin_memcpy(o.a, &a, sizeof(a));
+  __builtin_memcpy(o.b, &b, sizeof(b));
+  o.ea = Tile::scale_exp(seed, tile, rc, g, 0xA, scaled);
+  o.eb = Tile::scale_exp(seed, tile, rc, g, 0xB, scaled);
+  const f32x4 acc = Tile::mfma(a, b, f32x4{0.f, 0.f, 0.f, 0.f}, o.ea, o.eb);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    o.acc[i] = acc[i];
+    o.expect[i] = Tile::expect(seed, tile, 4 * g + i, rc, scaled);
+  }
+  lanes[lane] = o;
 }
 
 // ---------------------------------------------------------------------------
@@ -359,6 +389,11 @@ void launch_check(int blocks, uint32_t seed, int rounds, int scaled, unsigned* c
     hipLaunchKernelGGL((mfma_check<Tile, decltype(pl)...>), dim3(blocks), dim3(kBlock), 0, nullptr, seed, rounds, scaled, cu_tiles,
                        cu_bad, pl...);
   });
+}
+
+template <class Tile>
+void launch_tile(uint32_t seed, uint32_t tile, int scaled, bgc_tile_lane* lanes) {
+  hipLaunchKernelGGL(mfma_tile<Tile>, dim3(1), dim3(64), 0, nullptr, seed, tile, scaled, lanes);
 }
 
 template <class Tile, bool kTimed>
@@ -626,6 +661,25 @@ int bgc_diag_mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint3
 int bgc_diag_mfma_lowp_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_lowp_check_plant* check,
                                int n_check, const bgc_lowp_rate_plant* rate, int n_rate, bgc_lowp_result* out) {
   return lowp_run(device, waves_per_cu, throughput_iters, seed, check, n_check, rate, n_rate, out);
+}
+
+int bgc_diag_mfma_tile(int device, int path, int scaled, uint32_t seed, uint32_t tile, bgc_tile_lane* lanes) {
+  if (!lanes || path < BGC_TILE_BF16 || path > BGC_TILE_FP4 || (scaled != 0 && scaled != 1) || (scaled && path == BGC_TILE_BF16)) {
+    g_last_error = "invalid arguments";
+    return 1;
+  }
+  HIP_TRY(hipSetDevice(device));
+  DeviceBuffer d;
+  HIP_TRY(d.alloc(64 * sizeof(bgc_tile_lane), true));
+  if (path == BGC_TILE_BF16) {
+    launch_tile<Bf16Tile>(seed, tile, scaled, d.as<bgc_tile_lane>());
+  } else {
+    with_mx_fmt(path == BGC_TILE_FP8 ? 0 : 4,
+                [&](auto fmt) { launch_tile<MxTile<decltype(fmt)::value>>(seed, tile, scaled, d.as<bgc_tile_lane>()); });
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(lanes, d.p, 64 * sizeof(bgc_tile_lane), hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int bgc_diag_burn(int device, int duration_ms, int waves_per_cu, uint32_t seed, bgc_burn_result* out) {

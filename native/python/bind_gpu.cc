@@ -107,6 +107,21 @@ std::string planted(const char* what, Fn entry, A... args) {
   return dump_nogil([&] { return bgc::gpu::Diag::instance().call(what, entry, args...); });
 }
 
+// A walk's result plus "chunk_list": [[device address, bytes], ...]
+Value with_chunk_list(Value v, const std::vector<bgc_walk_chunk>& chunks) {
+  Value list = Value::array();
+  for (int c = 0; c < v.get("chunks").as_int() && c < count(chunks); ++c) {
+    const bgc_walk_chunk& one = chunks[static_cast<size_t>(c)];
+    list.push_back(Value::array({static_cast<unsigned long long>(one.base), static_cast<unsigned long long>(one.bytes)}));
+  }
+  v["chunk_list"] = list;
+  return v;
+}
+
+// The host buffer a generated-data entry fills.  A size beyond the library's cap gets an empty one:
+// the library refuses that call before it writes.
+std::string data_buffer(unsigned long long bytes) { return std::string(bytes <= BGC_DIAG_MAX_DATA_BYTES ? bytes : 0, '\0'); }
+
 }  // namespace
 
 void register_gpu(py::module_& m) {
@@ -278,15 +293,9 @@ void register_gpu(py::module_& m) {
     for (const auto& [pass, chunk, offset, mask] : plants) p.push_back({pass, chunk, offset, mask});
     std::vector<bgc_walk_chunk> chunks(1024);
     return dump_nogil([&] {
-      Value v = Diag::instance().call("hbm walk", BGC_DIAG_ENTRY(bgc_diag_hbm_walk_planted), device, bytes, chunk_bytes,
-                                      seed, p.data(), count(p), chunks.data(), count(chunks));
-      Value list = Value::array();  // the walk's result plus "chunk_list": [[device address, bytes], ...]
-      for (int c = 0; c < v.get("chunks").as_int() && c < count(chunks); ++c) {
-        const bgc_walk_chunk& one = chunks[static_cast<size_t>(c)];
-        list.push_back(Value::array({static_cast<u64>(one.base), static_cast<u64>(one.bytes)}));
-      }
-      v["chunk_list"] = list;
-      return v;
+      return with_chunk_list(Diag::instance().call("hbm walk", BGC_DIAG_ENTRY(bgc_diag_hbm_walk_planted), device, bytes,
+                                                   chunk_bytes, seed, p.data(), count(p), chunks.data(), count(chunks)),
+                             chunks);
     });
   }, py::arg("device"), py::arg("bytes"), py::arg("chunk_bytes"), py::arg("seed"), py::arg("plants"));
   m.def("diag_pcie_planted", [](int device, u64 bytes, unsigned seed, const std::vector<std::tuple<u64, u64>>& plants) {
@@ -323,6 +332,52 @@ void register_gpu(py::module_& m) {
     return planted("gemm soak", BGC_DIAG_ENTRY(bgc_diag_gemm_soak_planted), device, mm, nn, kk, launches, seed, p.data(),
                    count(p));
   }, py::arg("device"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("launches"), py::arg("seed"), py::arg("plants"));
+  // Generated data (gpu_diag.h): for tests only and resolved here alike.  Each returns the result JSON
+  // followed by the data as bytes.
+  m.def("diag_hbm_data", [](int device, u64 bytes, int iters, unsigned seed) {
+    std::string data = data_buffer(bytes & ~15ULL);
+    const std::string r = planted("hbm diag", BGC_DIAG_ENTRY(bgc_diag_hbm_data), device, bytes, iters, seed,
+                                  static_cast<void*>(data.data()));
+    return py::make_tuple(r, py::bytes(data));
+  }, py::arg("device"), py::arg("bytes"), py::arg("iters"), py::arg("seed"));
+  m.def("diag_hbm_walk_data", [](int device, u64 bytes, u64 chunk_bytes, int passes, unsigned seed) {
+    std::string data = data_buffer(bytes & ~((2ULL << 20) - 1));
+    std::vector<bgc_walk_chunk> chunks(64);  // 128 MiB at most, in chunks of at least 64 MiB
+    const std::string r = dump_nogil([&] {
+      return with_chunk_list(Diag::instance().call("hbm walk", BGC_DIAG_ENTRY(bgc_diag_hbm_walk_data), device, bytes, chunk_bytes,
+                                                   passes, seed, chunks.data(), count(chunks), static_cast<void*>(data.data())),
+                             chunks);
+    });
+    return py::make_tuple(r, py::bytes(data));
+  }, py::arg("device"), py::arg("bytes"), py::arg("chunk_bytes"), py::arg("passes"), py::arg("seed"));
+  m.def("diag_pcie_data", [](int device, u64 bytes, unsigned seed) {
+    std::string data = data_buffer(bytes & ~7ULL);
+    const std::string r = planted("pcie diag", BGC_DIAG_ENTRY(bgc_diag_pcie_data), device, bytes, seed, static_cast<void*>(data.data()));
+    return py::make_tuple(r, py::bytes(data));
+  }, py::arg("device"), py::arg("bytes"), py::arg("seed"));
+  m.def("diag_gemm_soak_data", [](int device, int mm, int nn, int kk, unsigned seed) {
+    // the sizes of a shape the library may accept; any other gets empty buffers and is refused there
+    const bool sized = mm > 0 && nn > 0 && kk > 0 && mm <= 32768 && nn <= 32768 && kk <= 32768;
+    const u64 um = sized ? mm : 0, un = sized ? nn : 0, uk = sized ? kk : 0;
+    const bool fits = 2 * um * uk + 2 * un * uk + 4 * um * un + 8 * (um + un) <= BGC_DIAG_MAX_DATA_BYTES;
+    auto buffer = [&](u64 bytes) { return std::string(fits ? bytes : 0, '\0'); };
+    std::string a = buffer(2 * um * uk), bt = buffer(2 * un * uk), rref = buffer(8 * um), cref = buffer(8 * un), c = buffer(4 * um * un);
+    const bgc_soak_data data = {reinterpret_cast<uint16_t*>(a.data()), reinterpret_cast<uint16_t*>(bt.data()),
+                                reinterpret_cast<int64_t*>(rref.data()), reinterpret_cast<int64_t*>(cref.data()),
+                                reinterpret_cast<float*>(c.data())};
+    const std::string r = planted("gemm soak", BGC_DIAG_ENTRY(bgc_diag_gemm_soak_data), device, mm, nn, kk, seed, &data);
+    return py::make_tuple(r, py::bytes(a), py::bytes(bt), py::bytes(rref), py::bytes(cref), py::bytes(c));
+  }, py::arg("device"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("seed"));
+  // the 64 bgc_tile_lane of one tile, as bytes
+  m.def("diag_mfma_tile", [](int device, int path, int scaled, unsigned seed, unsigned tile) {
+    std::string lanes(64 * sizeof(bgc_tile_lane), '\0');
+    {
+      py::gil_scoped_release nogil;
+      Diag::instance().check("mfma tile", BGC_DIAG_ENTRY(bgc_diag_mfma_tile)(device, path, scaled, seed, tile,
+                                                                             reinterpret_cast<bgc_tile_lane*>(lanes.data())));
+    }
+    return py::bytes(lanes);
+  }, py::arg("device"), py::arg("path"), py::arg("scaled"), py::arg("seed"), py::arg("tile"));
 #undef BGC_DIAG_ENTRY
   m.def("pcie_check", [](std::shared_ptr<PyBackend> b, int index, int hip_device, unsigned long long bytes, unsigned seed) {
     return dump_nogil([&] {

@@ -59,6 +59,16 @@ REFUSED = {
                           "low-precision mfma diag: invalid arguments"),
     "gemm_soak_planted": (lambda n: n.diag_gemm_soak_planted(0, 256, 256, 128, 1, SEED, [(0, 300, 0, 1.0)]), RuntimeError,
                           "gemm soak: invalid arguments: " + SOAK_SHAPE + "; plants inside C, on the first or the last launch"),
+    "hbm_data": (lambda n: n.diag_hbm_data(0, 129 * MIB, 1, SEED), RuntimeError, "hbm diag: invalid arguments"),
+    "pcie_data": (lambda n: n.diag_pcie_data(0, 129 * MIB, SEED), RuntimeError, "pcie diag: invalid arguments"),
+    "hbm_walk_data": (lambda n: n.diag_hbm_walk_data(0, 130 * MIB, 64 * MIB, 2, SEED), RuntimeError,
+                      "hbm walk: invalid arguments: 2 MiB <= bytes <= 128 MiB, chunk_bytes >= 64 MiB, 1 or 2 passes, room for "
+                      "every chunk"),
+    "gemm_soak_data": (lambda n: n.diag_gemm_soak_data(0, 8192, 8192, 128, SEED), RuntimeError,
+                       "gemm soak: invalid arguments: five destinations, and at most 128 MiB to return"),
+    "gemm_soak_data_shape": (lambda n: n.diag_gemm_soak_data(0, 100, 128, 64, SEED), RuntimeError,
+                             "gemm soak: invalid arguments: " + SOAK_SHAPE),
+    "mfma_tile": (lambda n: n.diag_mfma_tile(0, 4, 0, SEED, 0), RuntimeError, "mfma tile: invalid arguments"),
 }
 
 

@@ -77,6 +77,66 @@ def test_soak_plant_outside_the_matrix_or_on_an_unverified_launch(nat, launches,
     _refused(nat.diag_gemm_soak_planted, 0, 256, 512, 128, launches, SEED, [(0, 0, 0, 1.0), plant])
 
 
+def test_generated_data_beyond_the_download_cap(nat):
+    """The generated-data variants (tests/gpu/test_diag_generated_data.py) copy what a diagnostic
+    generated back to the host: at most 128 MiB per call."""
+    cap = 128 * MIB
+    _refused(nat.diag_hbm_data, 0, cap + 16, 1, SEED)
+    _refused(nat.diag_hbm_data, 0, 1 << 40, 1, SEED)
+    _refused(nat.diag_hbm_data, 0, MIB, 0, SEED)  # and what bgc_diag_hbm refuses
+    _refused(nat.diag_pcie_data, 0, cap + 8, SEED)
+    _refused(nat.diag_pcie_data, 0, MIB - 8, SEED)
+    _refused(nat.diag_hbm_walk_data, 0, cap + 2 * MIB, 64 * MIB, 1, SEED)
+    _refused(nat.diag_hbm_walk_data, 0, MIB, 64 * MIB, 1, SEED)  # nothing left after rounding to 2 MiB
+    _refused(nat.diag_hbm_walk_data, 0, 66 * MIB, 64 * MIB - 1, 1, SEED)
+    _refused(nat.diag_hbm_walk_data, 0, 66 * MIB, 64 * MIB, 0, SEED)  # one or two passes
+    _refused(nat.diag_hbm_walk_data, 0, 66 * MIB, 64 * MIB, 3, SEED)
+    _refused(nat.diag_gemm_soak_data, 0, 4096, 4096, 4096, SEED)  # 128 MiB of operands and C, and the checksums
+    _refused(nat.diag_gemm_soak_data, 0, 32768, 32768, 32768, SEED)
+    _refused(nat.diag_gemm_soak_data, 0, 256, 200, 128, SEED)  # and what bgc_diag_gemm_soak refuses
+    _refused(nat.diag_gemm_soak_data, 0, -256, 256, 128, SEED)
+
+
+@pytest.mark.parametrize("path,scaled", [(3, 0), (-1, 0), (0, 1), (1, 2), (2, -1)],
+                         ids=["path_3", "path_-1", "bf16_scaled", "scaled_2", "scaled_-1"])
+def test_mfma_tile_path_or_scaling_out_of_range(nat, path, scaled):
+    _refused(nat.diag_mfma_tile, 0, path, scaled, SEED, 0)
+
+
+def test_generated_data_without_a_destination():
+    """The bindings always pass buffers, so the null destinations go to the C ABI directly."""
+    from bacchus_gpu_controller_amd.utils.build import gpu_diag_path
+
+    lib = ctypes.CDLL(gpu_diag_path())
+    lib.bgc_diag_last_error.restype = ctypes.c_char_p
+    out = ctypes.create_string_buffer(4096)  # larger than any result struct
+    room = ctypes.create_string_buffer(4096)
+    u64, u32, i32, ptr = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p
+
+    def soak_data(missing):
+        return (ptr * 5)(*[None if i == missing else ctypes.addressof(room) for i in range(5)])
+
+    calls = [
+        (lib.bgc_diag_hbm_data, [i32(0), u64(MIB), i32(1), u32(SEED), None, out]),
+        (lib.bgc_diag_hbm_data, [i32(0), u64(MIB), i32(1), u32(SEED), room, None]),
+        (lib.bgc_diag_pcie_data, [i32(0), u64(MIB), u32(SEED), None, out]),
+        (lib.bgc_diag_pcie_data, [i32(0), u64(MIB), u32(SEED), room, None]),
+        (lib.bgc_diag_hbm_walk_data, [i32(0), u64(66 * MIB), u64(64 * MIB), i32(1), u32(SEED), room, i32(2), None, out]),
+        (lib.bgc_diag_hbm_walk_data, [i32(0), u64(66 * MIB), u64(64 * MIB), i32(1), u32(SEED), None, i32(2), room, out]),
+        (lib.bgc_diag_hbm_walk_data, [i32(0), u64(66 * MIB), u64(64 * MIB), i32(1), u32(SEED), room, i32(2), room, None]),
+        # two chunks, room for one
+        (lib.bgc_diag_hbm_walk_data, [i32(0), u64(66 * MIB), u64(64 * MIB), i32(1), u32(SEED), room, i32(1), room, out]),
+        (lib.bgc_diag_gemm_soak_data, [i32(0), i32(256), i32(256), i32(128), u32(SEED), None, out]),
+        (lib.bgc_diag_gemm_soak_data, [i32(0), i32(256), i32(256), i32(128), u32(SEED), soak_data(None), None]),
+        *[(lib.bgc_diag_gemm_soak_data, [i32(0), i32(256), i32(256), i32(128), u32(SEED), soak_data(i), out]) for i in range(5)],
+        (lib.bgc_diag_mfma_tile, [i32(0), i32(0), i32(0), u32(SEED), u32(0), None]),
+    ]
+    for fn, args in calls:
+        fn.restype = ctypes.c_int
+        assert fn(*args) != 0, fn.__name__
+        assert lib.bgc_diag_last_error().decode().startswith("invalid arguments"), (fn.__name__, lib.bgc_diag_last_error())
+
+
 def test_negative_plant_count():
     """A Python list cannot have a negative length, so this one goes to the C ABI directly."""
     from bacchus_gpu_controller_amd.utils.build import gpu_diag_path
