@@ -26,6 +26,8 @@ These are the only compute kernels in the framework: the reference controller ha
 * ``hbm_planted``, ``hbm_walk_planted``, ``pcie_planted``, ``mfma_planted``,
   ``mfma_lowp_planted``, ``gemm_soak_planted`` — for tests: the same diagnostics with wrong
   values planted in their own data, to show that they are detected (see below)
+* ``mfma_delayed``, ``burn_delayed`` — for tests: the matrix-core throughput and the burn with
+  chosen waves or launches made slow by a known time, to show that it reaches the rates
 * ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile`` — for tests:
   the same diagnostics, returning the data they generated for themselves (see below)
 
@@ -131,6 +133,22 @@ def mfma_lowp_planted(check_plants, rate_plants=(), device=0, waves_per_cu=1, it
     check = [(_LOWP_VARIANTS[p[0]],) + tuple(p[1:]) for p in check_plants]
     rate = [(_LOWP_FORMATS[p[0]],) + tuple(p[1:]) for p in rate_plants]
     return json.loads(native().diag_mfma_lowp_planted(device, waves_per_cu, iters, seed, check, rate))
+
+
+MAX_DELAY_TICKS = 10_000_000  # 100 ms of the 100 MHz constant clock
+
+
+def mfma_delayed(delays, device=0, waves_per_cu=1, iters=64, seed=0x5EED):
+    """`delays` = [(wave or ALL_WAVES, ticks), ...]: in the timed throughput launch that wave waits,
+    after its loop and before its comparison, until `ticks` of the 100 MHz constant clock have
+    passed.  Its values are untouched; its time shows in tflops, xcc_wave_us and xcc_balance."""
+    return json.loads(native().diag_mfma_delayed(device, waves_per_cu, iters, seed, list(delays)))
+
+
+def burn_delayed(duration_ms, first_delayed_launch, ticks, dtype="bf16", device=0, waves_per_cu=32, seed=0x5EED):
+    """The burn's loop (without the telemetry that ``diag_burn`` adds) with every wave of launch
+    `first_delayed_launch` (0-based) and of every later one delayed by `ticks`."""
+    return json.loads(native().diag_burn_delayed(device, duration_ms, waves_per_cu, seed, dtype, first_delayed_launch, ticks))
 
 
 def gemm_soak_planted(m, n, k, launches, plants, device=0, seed=0x5EED):

@@ -219,10 +219,8 @@ json::Value Diag::hbm_walk(int device, double fraction, uint64_t chunk_bytes, in
   return call("hbm walk", walk_, device, fraction, chunk_bytes, budget_ms, seed);
 }
 
-// The burn's JSON carries an argument (the dtype) and no device, so it is written out here.
-json::Value Diag::burn(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype) {
-  bgc_burn_result r{};
-  check("burn", burn_(device, duration_ms, waves_per_cu, seed, dtype, &r));
+// The burn's JSON carries an argument (the dtype) and no device.
+json::Value to_json(const bgc_burn_result& r, int dtype) {
   return json::Value::object({{"dtype", burn_dtype_name(dtype)}, {"launches", r.launches},
                               {"elapsed_ms", r.elapsed_ms}, {"tflops_mean", r.tflops_mean},
                               {"tflops_min", r.tflops_min}, {"tflops_first", r.tflops_first},
@@ -230,6 +228,12 @@ json::Value Diag::burn(int device, int duration_ms, int waves_per_cu, uint32_t s
                               // the last launch against the best: < 1 when the GPU throttled
                               {"sustain", r.tflops_max > 0 ? r.tflops_last / r.tflops_max : 0.0},
                               {"mismatches", static_cast<unsigned long long>(r.mismatches)}});
+}
+
+json::Value Diag::burn(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype) {
+  bgc_burn_result r{};
+  check("burn", burn_(device, duration_ms, waves_per_cu, seed, dtype, &r));
+  return to_json(r, dtype);
 }
 
 void Diag::gemm(int device, int m, int n, int k, const uint16_t* a, const uint16_t* b, float* c) {

@@ -82,6 +82,8 @@ json::Value to_json(int device, const bgc_lowp_result& r);
 json::Value to_json(int device, const bgc_pcie_result& r);
 json::Value to_json(int device, const bgc_soak_result& r);
 json::Value to_json(int device, const bgc_hbm_walk_result& r);
+// The burn's JSON names its dtype (BGC_BURN_*) instead of a device.
+json::Value to_json(const bgc_burn_result& r, int dtype);
 
 class Diag {
  public:

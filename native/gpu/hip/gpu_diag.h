@@ -15,7 +15,7 @@
 extern "C" {
 #endif
 
-#define BGC_DIAG_ABI_VERSION 13
+#define BGC_DIAG_ABI_VERSION 14
 #define BGC_DIAG_MAX_CU_KEYS 2048
 
 // The data the diagnostics generate for themselves.  All arithmetic is modulo 2^32 (mix32) or
@@ -204,8 +204,9 @@ int bgc_diag_hbm_walk(int device, double fraction, uint64_t chunk_bytes, int bud
 // Planted variants: FOR TESTS ONLY.  Each runs the same implementation as the entry point it is
 // named after, with a list of deliberately wrong values ("plants") written into the diagnostic's
 // own buffers or accumulators between the phase that produces the data and the phase that checks
-// it, so a test can show that a wrong value reaches the counters.  An empty list is the production
-// behaviour.  Every plant is in bounds: a position outside the buffer, or a wave, lane, round,
+// it, so a test can show that a wrong value reaches the counters; the *_delayed variants plant time
+// instead, so a test can show that a slow wave or launch reaches the rates.  An empty list is the
+// production behaviour.  Every plant is in bounds: a position outside the buffer, or a wave, lane, round,
 // chain or element index out of range, a negative count or more than BGC_DIAG_MAX_PLANTS is
 // refused with "invalid arguments" before the device is touched (only `wave` has to wait for the
 // device's CU count).  The node agent and the diag worker never load these symbols.
@@ -276,6 +277,32 @@ typedef struct {
 int bgc_diag_mfma_lowp_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
                                const bgc_lowp_check_plant* check, int n_check, const bgc_lowp_rate_plant* rate,
                                int n_rate, bgc_lowp_result* out);
+
+// Delay plants: time instead of values.  Wave `wave` (global wave index, or BGC_PLANT_ALL_WAVES) of a
+// throughput launch reaches the plant point after its loop and before its comparison, where the
+// value plants above are applied.  There it waits until `ticks` of the constant clock (wall_clock64(),
+// 100 MHz: the clock xcc_wave_us is measured with) have passed since it reached that point, and goes
+// on; the wait is a loop on the clock difference with s_sleep between the reads and nothing else, so
+// it ends after `ticks` whatever else happens, and the wave's values are untouched.  A wave that
+// several plants name waits for the largest of their `ticks`.  `ticks` is 1..BGC_DIAG_MAX_DELAY_TICKS
+// (100 ms at 100 MHz); 0, more, or `wave` < BGC_PLANT_ALL_WAVES is refused with "invalid arguments"
+// before the device is touched.
+#define BGC_DIAG_MAX_DELAY_TICKS 10000000u
+typedef struct {
+  int wave;
+  uint32_t ticks;
+} bgc_mfma_delay_plant;
+// bgc_diag_mfma with `delays` applied in the timed throughput launch only: the warm-up launch and the
+// check phase take none.  So the delayed waves' time shows in tflops, xcc_wave_us and xcc_balance, and
+// nothing else of the result moves.
+int bgc_diag_mfma_delayed(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
+                          const bgc_mfma_delay_plant* delays, int n, bgc_mfma_result* out);
+// bgc_diag_burn_dtype with every wave of every launch whose index (0-based) is at least
+// `first_delayed_launch` (>= 0) delayed by `ticks`; a `first_delayed_launch` the burn never reaches
+// is a clean burn.  The MX rate kernels do not time themselves, which is why the delay counts from
+// the plant point and not from the kernel's start.
+int bgc_diag_burn_delayed(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype,
+                          int first_delayed_launch, uint32_t ticks, bgc_burn_result* out);
 
 // C[row][col] += delta after launch `launch` and before its checksums.  Only the first and the
 // last launch are verified: a plant on any other launch is invalid.

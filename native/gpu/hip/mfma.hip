@@ -18,6 +18,8 @@
 //    (with_plants); each fills its own result struct.
 //  * bgc_diag_mfma_tile runs one round of the check in one wave (mfma_tile) and returns what every
 //    lane held, for the tests of the generated tiles.
+//  * bgc_diag_mfma_delayed and bgc_diag_burn_delayed make chosen waves of a throughput launch wait on
+//    the constant clock (delay()), for the tests of the rates and times.
 #include <algorithm>
 #include <cstring>
 #include <utility>
@@ -159,8 +161,9 @@ struct MxTile {
 
 // Test plants (gpu_diag.h, "planted variants").  The check and throughput kernels end in a pack
 // `Plants... plants`: empty in the production instantiations, which so take no further argument and
-// call the empty plant() overloads (they compile to what they would be without), and one plant list
-// in the instantiations behind the *_planted entry points.  Everything else, the comparison, the
+// call the empty plant() and delay() overloads (they compile to what they would be without), and one
+// plant list in the instantiations behind the *_planted entry points (wrong values) and the *_delayed
+// ones (DelayPlants: waits on the constant clock).  Everything else, the comparison, the
 // wave reduction and the report, is the same source for both; with_plants() below picks between them.
 template <class P>
 struct PlantList {  // in device memory
@@ -169,6 +172,7 @@ struct PlantList {  // in device memory
 };
 using CheckPlants = PlantList<bgc_mfma_check_plant>;
 using RatePlants = PlantList<bgc_mfma_rate_plant>;
+using DelayPlants = PlantList<bgc_mfma_delay_plant>;
 
 __device__ __forceinline__ void add_at(f32x4& acc, int i, float delta) {
 #pragma unroll
@@ -199,6 +203,23 @@ __device__ __forceinline__ void plant(f32x4 (&acc)[4], uint32_t wave, int lane, 
       if (c == p.chain) add_at(acc[c], p.i, p.delta);
     }
   }
+}
+__device__ __forceinline__ void plant(f32x4 (&)[4], uint32_t /*wave*/, int /*lane*/, DelayPlants) {}  // no values
+
+// throughput phase, at the same point: the wave waits for the largest `ticks` of the delay plants
+// that name it, counted on the constant clock from here.  The loop's only exit condition is the clock
+// difference, so it ends after `ticks` (at most BGC_DIAG_MAX_DELAY_TICKS, checked on the host).
+__device__ __forceinline__ void delay(uint32_t /*wave*/) {}
+__device__ __forceinline__ void delay(uint32_t /*wave*/, RatePlants) {}
+__device__ __forceinline__ void delay(uint32_t wave, DelayPlants pl) {
+  uint32_t ticks = 0;
+  for (int j = 0; j < pl.n; ++j) {
+    const bgc_mfma_delay_plant p = pl.p[j];
+    if (p.wave == BGC_PLANT_ALL_WAVES || static_cast<uint32_t>(p.wave) == wave) ticks = max(ticks, p.ticks);
+  }
+  ticks = __builtin_amdgcn_readfirstlane(ticks);  // the same in every lane of the wave
+  const uint64_t t0 = wall_clock64();
+  while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
 }
 
 // ---------------------------------------------------------------------------
@@ -275,6 +296,7 @@ __global__ __launch_bounds__(kBlock) void mfma_throughput(uint32_t seed, int ite
     for (int c = 0; c < 4; ++c) acc[c] = Tile::mfma(a, b, acc[c], 0, 0);
   }
   plant(acc, tile, lane, plants...);
+  delay(tile, plants...);
   unsigned bad = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -396,17 +418,19 @@ void launch_tile(uint32_t seed, uint32_t tile, int scaled, bgc_tile_lane* lanes)
   hipLaunchKernelGGL(mfma_tile<Tile>, dim3(1), dim3(64), 0, nullptr, seed, tile, scaled, lanes);
 }
 
-template <class Tile, bool kTimed>
-void launch_rate(int blocks, uint32_t seed, int iters, unsigned* fails, unsigned long long* xt, unsigned* xw, RatePlants plants) {
+template <class Tile, bool kTimed, class P>
+void launch_rate(int blocks, uint32_t seed, int iters, unsigned* fails, unsigned long long* xt, unsigned* xw, PlantList<P> plants) {
   with_plants(plants, [&](auto... pl) {
     hipLaunchKernelGGL((mfma_throughput<Tile, kTimed, decltype(pl)...>), dim3(blocks), dim3(kBlock), 0, nullptr, seed, iters, fails,
                        xt, xw, pl...);
   });
 }
 
-// one throughput launch of a burn dtype: bf16 (timed per XCC into xt / xw) or MX fp8 / fp4
+// one throughput launch of a burn dtype: bf16 (timed per XCC into xt / xw) or MX fp8 / fp4; the
+// plants are value plants (RatePlants) or delay plants (DelayPlants)
+template <class P = bgc_mfma_rate_plant>
 void launch_throughput(int dtype, int blocks, uint32_t seed, int iters, unsigned* fails, unsigned long long* xt = nullptr,
-                       unsigned* xw = nullptr, RatePlants plants = {}) {
+                       unsigned* xw = nullptr, PlantList<P> plants = {}) {
   if (dtype == BGC_BURN_BF16) {
     launch_rate<Bf16Tile, true>(blocks, seed, iters, fails, xt, xw, plants);
   } else {
@@ -425,15 +449,18 @@ bool check_plant_ok(const bgc_mfma_check_plant& p, int rounds) {
 bool rate_plant_ok(const bgc_mfma_rate_plant& p) {
   return p.wave >= 0 && p.lane >= 0 && p.lane < 64 && p.chain >= 0 && p.chain < 4 && p.i >= 0 && p.i < 4;
 }
+bool delay_ticks_ok(uint32_t ticks) { return ticks > 0 && ticks <= BGC_DIAG_MAX_DELAY_TICKS; }
+bool delay_plant_ok(const bgc_mfma_delay_plant& p) { return p.wave >= BGC_PLANT_ALL_WAVES && delay_ticks_ok(p.ticks); }
 
 // (launch, place in it) of a test plant: an MX plant names its check variant or rate format, the
 // bf16 run has one launch of each kind.
 std::pair<int, bgc_mfma_check_plant> split(const bgc_mfma_check_plant& p) { return {0, p}; }
 std::pair<int, bgc_mfma_rate_plant> split(const bgc_mfma_rate_plant& p) { return {0, p}; }
+std::pair<int, bgc_mfma_delay_plant> split(const bgc_mfma_delay_plant& p) { return {0, p}; }
 std::pair<int, bgc_mfma_check_plant> split(const bgc_lowp_check_plant& p) { return {p.variant, p.at}; }
 std::pair<int, bgc_mfma_rate_plant> split(const bgc_lowp_rate_plant& p) { return {p.fmt, p.at}; }
 
-// The check-phase or the rate-phase plants of one run, sorted by the launch they belong to.
+// The check-phase, the rate-phase or the delay plants of one run, sorted by the launch they belong to.
 template <class At>
 struct HostPlants {
   std::vector<At> host[4];
@@ -516,20 +543,21 @@ double rate_flops(int blocks, int iters) {
 }
 
 int mfma_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_mfma_check_plant* check, int n_check,
-             const bgc_mfma_rate_plant* rate, int n_rate, bgc_mfma_result* out) {
+             const bgc_mfma_rate_plant* rate, int n_rate, const bgc_mfma_delay_plant* delays, int n_delay, bgc_mfma_result* out) {
   const int rounds = BGC_MFMA_CHECK_ROUNDS;
   HostPlants<bgc_mfma_check_plant> check_plants;
   HostPlants<bgc_mfma_rate_plant> rate_plants;
+  HostPlants<bgc_mfma_delay_plant> delay_plants;  // no entry point takes both these and rate plants
   if (!(out && waves_per_cu > 0 && throughput_iters > 0 && throughput_iters <= (1 << 18) &&
         check_plants.take(check, n_check, 1, [&](const auto& at) { return check_plant_ok(at, rounds); }) &&
-        rate_plants.take(rate, n_rate, 1, rate_plant_ok))) {
+        rate_plants.take(rate, n_rate, 1, rate_plant_ok) && delay_plants.take(delays, n_delay, 1, delay_plant_ok))) {
     g_last_error = "invalid arguments";
     return 1;
   }
   std::memset(out, 0, sizeof(*out));
   HIP_TRY(hipSetDevice(device));
   const int blocks = wave_blocks(device, waves_per_cu);
-  if (check_plants.upload(blocks) != 0 || rate_plants.upload(blocks) != 0) return 1;
+  if (check_plants.upload(blocks) != 0 || rate_plants.upload(blocks) != 0 || delay_plants.upload(blocks) != 0) return 1;
   CuBins<1> bins;
   if (bins.alloc() != 0) return 1;
   DeviceBuffer fails, xticks, xwaves;
@@ -552,7 +580,11 @@ int mfma_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, 
   HIP_TRY(hipMemset(xticks.p, 0, 8 * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(xwaves.p, 0, 8 * sizeof(unsigned)));
   if (timed(ev, &ms_tp, [&] {
-        launch_throughput(BGC_BURN_BF16, blocks, seed, throughput_iters, fails.as<unsigned>(), xt, xw, rate_plants.of(0));
+        if (n_delay > 0) {
+          launch_throughput(BGC_BURN_BF16, blocks, seed, throughput_iters, fails.as<unsigned>(), xt, xw, delay_plants.of(0));
+        } else {
+          launch_throughput(BGC_BURN_BF16, blocks, seed, throughput_iters, fails.as<unsigned>(), xt, xw, rate_plants.of(0));
+        }
       }) != 0) {
     return 1;
   }
@@ -641,17 +673,90 @@ int lowp_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, 
   return 0;
 }
 
+// bgc_diag_burn_dtype, and bgc_diag_burn_delayed with every wave of the launches from `first_delayed_launch`
+// on delayed by `ticks` (0: no launch is delayed, the production burn)
+int burn_run(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype, int first_delayed_launch, uint32_t ticks,
+             bgc_burn_result* out) {
+  if (!out || duration_ms <= 0 || duration_ms > 600000 || waves_per_cu <= 0 || waves_per_cu > 64 ||
+      dtype < BGC_BURN_BF16 || dtype > BGC_BURN_FP4) {
+    g_last_error = "invalid arguments";
+    return 1;
+  }
+  std::memset(out, 0, sizeof(*out));
+  HIP_TRY(hipSetDevice(device));
+  const int blocks = wave_blocks(device, waves_per_cu);
+  HostPlants<bgc_mfma_delay_plant> delay_plants;
+  if (ticks > 0) {
+    delay_plants.host[0].push_back({BGC_PLANT_ALL_WAVES, ticks});
+    if (delay_plants.upload(blocks) != 0) return 1;
+  }
+  DeviceBuffer fails, xticks, xwaves;
+  HIP_TRY(fails.alloc(sizeof(unsigned), true));
+  HIP_TRY(xticks.alloc(8 * sizeof(unsigned long long)));
+  HIP_TRY(xwaves.alloc(8 * sizeof(unsigned)));
+  Events ev, total;
+  HIP_TRY(ev.create());
+  HIP_TRY(total.create());
+  // size one launch to ~10 ms at MI355X rates (iters * 4 MFMA per wave), measured below
+  int iters = 2048;
+  const double flops_per_iter = dtype == BGC_BURN_BF16 ? rate_flops<Bf16Tile>(blocks, 1) : rate_flops<MxTile<0>>(blocks, 1);
+  float ms = 0.f;
+  HIP_TRY(hipEventRecord(total.a, nullptr));
+  double sum_flops = 0;
+  while (true) {
+    if (timed(ev, &ms, [&] {
+          if (ticks > 0 && out->launches >= first_delayed_launch) {
+            launch_throughput(dtype, blocks, seed, iters, fails.as<unsigned>(), xticks.as<unsigned long long>(), xwaves.as<unsigned>(),
+                              delay_plants.of(0));
+          } else {
+            launch_throughput(dtype, blocks, seed, iters, fails.as<unsigned>(), xticks.as<unsigned long long>(), xwaves.as<unsigned>());
+          }
+        }) != 0) {
+      return 1;
+    }
+    const double tf = flops_per_iter * iters / (ms * 1e-3) / 1e12;
+    out->tflops_max = std::max(out->tflops_max, tf);
+    if (out->launches == 0) {
+      out->tflops_first = tf;
+      out->tflops_min = tf;
+      // retune the launch length to ~10 ms now that the rate is known
+      iters = std::max(64, std::min(1 << 18, static_cast<int>(iters * (10.0 / std::max(0.01f, ms)))));
+    } else {
+      out->tflops_min = std::min(out->tflops_min, tf);
+    }
+    out->tflops_last = tf;
+    out->launches++;
+    sum_flops += flops_per_iter * (out->launches == 1 ? 2048 : iters);
+    HIP_TRY(hipEventRecord(total.b, nullptr));
+    HIP_TRY(hipEventSynchronize(total.b));
+    float so_far = 0.f;
+    HIP_TRY(hipEventElapsedTime(&so_far, total.a, total.b));
+    out->elapsed_ms = so_far;
+    if (so_far >= static_cast<float>(duration_ms)) break;
+  }
+  unsigned h_fails = 0;
+  HIP_TRY(hipMemcpy(&h_fails, fails.p, sizeof(unsigned), hipMemcpyDeviceToHost));
+  out->mismatches = h_fails;
+  out->tflops_mean = sum_flops / (out->elapsed_ms * 1e-3) / 1e12;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
 
 int bgc_diag_mfma(int device, int waves_per_cu, int throughput_iters, uint32_t seed, bgc_mfma_result* out) {
-  return mfma_run(device, waves_per_cu, throughput_iters, seed, nullptr, 0, nullptr, 0, out);
+  return mfma_run(device, waves_per_cu, throughput_iters, seed, nullptr, 0, nullptr, 0, nullptr, 0, out);
 }
 
 int bgc_diag_mfma_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_mfma_check_plant* check,
                           int n_check, const bgc_mfma_rate_plant* rate, int n_rate, bgc_mfma_result* out) {
-  return mfma_run(device, waves_per_cu, throughput_iters, seed, check, n_check, rate, n_rate, out);
+  return mfma_run(device, waves_per_cu, throughput_iters, seed, check, n_check, rate, n_rate, nullptr, 0, out);
+}
+
+int bgc_diag_mfma_delayed(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_mfma_delay_plant* delays, int n,
+                          bgc_mfma_result* out) {
+  return mfma_run(device, waves_per_cu, throughput_iters, seed, nullptr, 0, nullptr, 0, delays, n, out);
 }
 
 int bgc_diag_mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint32_t seed, bgc_lowp_result* out) {
@@ -687,58 +792,16 @@ int bgc_diag_burn(int device, int duration_ms, int waves_per_cu, uint32_t seed, 
 }
 
 int bgc_diag_burn_dtype(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype, bgc_burn_result* out) {
-  if (!out || duration_ms <= 0 || duration_ms > 600000 || waves_per_cu <= 0 || waves_per_cu > 64 ||
-      dtype < BGC_BURN_BF16 || dtype > BGC_BURN_FP4) {
+  return burn_run(device, duration_ms, waves_per_cu, seed, dtype, 0, 0, out);
+}
+
+int bgc_diag_burn_delayed(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype, int first_delayed_launch,
+                          uint32_t ticks, bgc_burn_result* out) {
+  if (first_delayed_launch < 0 || !delay_ticks_ok(ticks)) {
     g_last_error = "invalid arguments";
     return 1;
   }
-  std::memset(out, 0, sizeof(*out));
-  HIP_TRY(hipSetDevice(device));
-  const int blocks = wave_blocks(device, waves_per_cu);
-  DeviceBuffer fails, xticks, xwaves;
-  HIP_TRY(fails.alloc(sizeof(unsigned), true));
-  HIP_TRY(xticks.alloc(8 * sizeof(unsigned long long)));
-  HIP_TRY(xwaves.alloc(8 * sizeof(unsigned)));
-  Events ev, total;
-  HIP_TRY(ev.create());
-  HIP_TRY(total.create());
-  // size one launch to ~10 ms at MI355X rates (iters * 4 MFMA per wave), measured below
-  int iters = 2048;
-  const double flops_per_iter = dtype == BGC_BURN_BF16 ? rate_flops<Bf16Tile>(blocks, 1) : rate_flops<MxTile<0>>(blocks, 1);
-  float ms = 0.f;
-  HIP_TRY(hipEventRecord(total.a, nullptr));
-  double sum_flops = 0;
-  while (true) {
-    if (timed(ev, &ms, [&] {
-          launch_throughput(dtype, blocks, seed, iters, fails.as<unsigned>(), xticks.as<unsigned long long>(), xwaves.as<unsigned>());
-        }) != 0) {
-      return 1;
-    }
-    const double tf = flops_per_iter * iters / (ms * 1e-3) / 1e12;
-    out->tflops_max = std::max(out->tflops_max, tf);
-    if (out->launches == 0) {
-      out->tflops_first = tf;
-      out->tflops_min = tf;
-      // retune the launch length to ~10 ms now that the rate is known
-      iters = std::max(64, std::min(1 << 18, static_cast<int>(iters * (10.0 / std::max(0.01f, ms)))));
-    } else {
-      out->tflops_min = std::min(out->tflops_min, tf);
-    }
-    out->tflops_last = tf;
-    out->launches++;
-    sum_flops += flops_per_iter * (out->launches == 1 ? 2048 : iters);
-    HIP_TRY(hipEventRecord(total.b, nullptr));
-    HIP_TRY(hipEventSynchronize(total.b));
-    float so_far = 0.f;
-    HIP_TRY(hipEventElapsedTime(&so_far, total.a, total.b));
-    out->elapsed_ms = so_far;
-    if (so_far >= static_cast<float>(duration_ms)) break;
-  }
-  unsigned h_fails = 0;
-  HIP_TRY(hipMemcpy(&h_fails, fails.p, sizeof(unsigned), hipMemcpyDeviceToHost));
-  out->mismatches = h_fails;
-  out->tflops_mean = sum_flops / (out->elapsed_ms * 1e-3) / 1e12;
-  return 0;
+  return burn_run(device, duration_ms, waves_per_cu, seed, dtype, first_delayed_launch, ticks, out);
 }
 
 int bgc_diag_gemm(int device, int m, int n, int k, const uint16_t* a_bf16, const uint16_t* b_bf16, float* c) {

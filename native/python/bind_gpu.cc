@@ -325,6 +325,25 @@ void register_gpu(py::module_& m) {
                    c.data(), count(c), r.data(), count(r));
   }, py::arg("device"), py::arg("waves_per_cu"), py::arg("iters"), py::arg("seed"), py::arg("check_plants"),
      py::arg("rate_plants"));
+  // Delay plants: (wave or -1, ticks of the constant clock) in the timed throughput launch; and a burn
+  // whose launches from `first_delayed_launch` on have every wave delayed by `ticks`.
+  m.def("diag_mfma_delayed", [](int device, int waves_per_cu, int iters, unsigned seed,
+                                const std::vector<std::tuple<int, unsigned>>& delays) {
+    std::vector<bgc_mfma_delay_plant> d;
+    for (const auto& [wave, ticks] : delays) d.push_back({wave, ticks});
+    return planted("mfma diag", BGC_DIAG_ENTRY(bgc_diag_mfma_delayed), device, waves_per_cu, iters, seed, d.data(), count(d));
+  }, py::arg("device"), py::arg("waves_per_cu"), py::arg("iters"), py::arg("seed"), py::arg("delays"));
+  m.def("diag_burn_delayed", [](int device, int duration_ms, int waves_per_cu, unsigned seed, const std::string& dtype,
+                                int first_delayed_launch, unsigned ticks) {
+    const int code = bgc::gpu::burn_dtype_code(dtype);
+    return dump_nogil([&] {
+      bgc_burn_result r{};
+      Diag::instance().check("burn", BGC_DIAG_ENTRY(bgc_diag_burn_delayed)(device, duration_ms, waves_per_cu, seed, code,
+                                                                           first_delayed_launch, ticks, &r));
+      return bgc::gpu::to_json(r, code);
+    });
+  }, py::arg("device"), py::arg("duration_ms"), py::arg("waves_per_cu"), py::arg("seed"), py::arg("dtype"),
+     py::arg("first_delayed_launch"), py::arg("ticks"));
   m.def("diag_gemm_soak_planted", [](int device, int mm, int nn, int kk, int launches, unsigned seed,
                                      const std::vector<std::tuple<int, int, int, float>>& plants) {
     std::vector<bgc_soak_plant> p;

@@ -62,6 +62,9 @@ CALLS = {
     "mfma_lowp_planted": (lambda ops: ops.mfma_lowp_planted([], []), LOWP),
     "gemm_soak_planted": (lambda ops: ops.gemm_soak_planted(256, 256, 128, 1, []), SOAK),
     "hbm_walk_planted": (lambda ops: ops.hbm_walk_planted(128 * MIB, 64 * MIB, []), WALK_PLANTED),
+    "mfma_delayed": (lambda ops: ops.mfma_delayed([]), MFMA),
+    # the burn's own keys, without the engine's and the sampler's
+    "burn_delayed": (lambda ops: ops.burn_delayed(200, 1 << 30, 1000), {k: BURN[k] for k in list(BURN)[:10]}),
 }
 
 

@@ -77,6 +77,34 @@ def test_soak_plant_outside_the_matrix_or_on_an_unverified_launch(nat, launches,
     _refused(nat.diag_gemm_soak_planted, 0, 256, 512, 128, launches, SEED, [(0, 0, 0, 1.0), plant])
 
 
+MAX_DELAY_TICKS = 10_000_000  # BGC_DIAG_MAX_DELAY_TICKS: 100 ms of the 100 MHz constant clock
+
+
+@pytest.mark.parametrize("delay", [(-2, 1000), (0, 0), (-1, 0), (0, MAX_DELAY_TICKS + 1), (-1, (1 << 32) - 1)],
+                         ids=["wave_-2", "ticks_0", "all_waves_ticks_0", "ticks_over_the_cap", "ticks_u32_max"])
+def test_mfma_delay_plant_out_of_range(nat, delay):
+    """A delay plant makes a wave wait in a loop on the clock, so the wait's length is bounded on the
+    host: 100 ms at most, and never 0 (a plant that does nothing is a mistake in the test)."""
+    _refused(nat.diag_mfma_delayed, 0, 1, 64, SEED, [(0, MAX_DELAY_TICKS), delay])
+
+
+def test_mfma_delay_plant_list_too_long(nat):
+    _refused(nat.diag_mfma_delayed, 0, 1, 64, SEED, [(0, 1000)] * 4097)  # BGC_DIAG_MAX_PLANTS is 4096
+
+
+@pytest.mark.parametrize("first,ticks,dtype", [(-1, 1000, "bf16"), (0, 0, "bf16"), (0, MAX_DELAY_TICKS + 1, "fp8"),
+                                               (1 << 30, (1 << 32) - 1, "fp4")],
+                         ids=["first_launch_-1", "ticks_0", "ticks_over_the_cap", "ticks_u32_max"])
+def test_burn_delay_out_of_range(nat, first, ticks, dtype):
+    _refused(nat.diag_burn_delayed, 0, 300, 32, SEED, dtype, first, ticks)
+
+
+@pytest.mark.parametrize("duration_ms,waves_per_cu", [(0, 32), (600001, 32), (300, 0), (300, 65)],
+                         ids=["duration_0", "duration_over_10_min", "waves_0", "waves_65"])
+def test_burn_delayed_refuses_what_the_burn_refuses(nat, duration_ms, waves_per_cu):
+    _refused(nat.diag_burn_delayed, 0, duration_ms, waves_per_cu, SEED, "bf16", 2, 1000)
+
+
 def test_generated_data_beyond_the_download_cap(nat):
     """The generated-data variants (tests/gpu/test_diag_generated_data.py) copy what a diagnostic
     generated back to the host: at most 128 MiB per call."""
@@ -156,6 +184,12 @@ def test_negative_plant_count():
         (lib.bgc_diag_mfma_lowp_planted, [i32(0), i32(1), i32(64), u32(SEED), plants, i32(-1), None, i32(0), out]),
         (lib.bgc_diag_mfma_lowp_planted, [i32(0), i32(1), i32(64), u32(SEED), None, i32(0), plants, i32(-1), out]),
         (lib.bgc_diag_gemm_soak_planted, [i32(0), i32(256), i32(256), i32(128), i32(1), u32(SEED), plants, i32(-1), out]),
+        (lib.bgc_diag_mfma_delayed, [i32(0), i32(1), i32(64), u32(SEED), plants, i32(-1), out]),
+        (lib.bgc_diag_mfma_delayed, [i32(0), i32(1), i32(64), u32(SEED), None, i32(1), out]),  # a count without a list
+        (lib.bgc_diag_mfma_delayed, [i32(0), i32(1), i32(64), u32(SEED), plants, i32(4097), out]),
+        (lib.bgc_diag_mfma_delayed, [i32(0), i32(1), i32(64), u32(SEED), None, i32(0), None]),  # no result struct
+        (lib.bgc_diag_burn_delayed, [i32(0), i32(300), i32(32), u32(SEED), i32(0), i32(2), u32(1000), None]),
+        (lib.bgc_diag_burn_delayed, [i32(0), i32(300), i32(32), u32(SEED), i32(3), i32(2), u32(1000), out]),  # no such dtype
     ]
     for fn, args in calls:
         fn.restype = ctypes.c_int
