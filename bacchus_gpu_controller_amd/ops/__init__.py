@@ -1,4 +1,4 @@
-"""HIP/CDNA4 GPU health kernels (native/gpu/hip/: hbm.hip, mfma.hip, gemm_soak.hip) exposed to Python.
+"""HIP/CDNA4 GPU health kernels (native/gpu/hip/: hbm.hip, mfma.hip, lds.hip, gemm_soak.hip) exposed to Python.
 
 These are the only compute kernels in the framework: the reference controller has none
 (SURVEY §2.5).  They back the node agent's diagnostics before a GPU is advertised
@@ -10,6 +10,8 @@ These are the only compute kernels in the framework: the reference controller ha
 * ``mfma(device)``      — exact-integer bf16 MFMA tiles on every CU + a throughput pass
 * ``mfma_lowp(device)`` — the same for the MX block-scaled fp8 / fp4 matrix-core path
   (``v_mfma_scale_f32_16x16x128_f8f6f4``), with and without E8M0 block scales
+* ``lds(device)``       — a march test of every CU's whole Local Data Share (160 KiB), attributed to
+  the CU, then the aggregate LDS read rate
 * ``gemm_check(device)``— a bf16 GEMM on the matrix cores checked element by element against
   a double-precision product of the same operands on the host
 * ``gemm_soak(device)`` — the sustained-throughput soak: the 8-phase ping-pong GEMM
@@ -24,11 +26,11 @@ These are the only compute kernels in the framework: the reference controller ha
 * ``pcie(device)``      — host<->device copy bandwidth, pinned
 * ``device_bdf(device)``— the HIP device's PCI address, to match it to amdsmi / kubelet
 * ``hbm_planted``, ``hbm_walk_planted``, ``pcie_planted``, ``mfma_planted``,
-  ``mfma_lowp_planted``, ``gemm_soak_planted`` — for tests: the same diagnostics with wrong
+  ``mfma_lowp_planted``, ``lds_planted``, ``gemm_soak_planted`` — for tests: the same diagnostics with wrong
   values planted in their own data, to show that they are detected (see below)
 * ``mfma_delayed``, ``burn_delayed`` — for tests: the matrix-core throughput and the burn with
   chosen waves or launches made slow by a known time, to show that it reaches the rates
-* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile`` — for tests:
+* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile``, ``lds_data`` — for tests:
   the same diagnostics, returning the data they generated for themselves (see below)
 
 All fail loudly (RuntimeError) if ``libbgc_gpu_diag.so`` or the GPU is missing; there
@@ -73,6 +75,13 @@ def mfma_lowp(device=0, waves_per_cu=32, iters=4096, seed=0x5EED):
     """MX block-scaled fp8 (e4m3) and fp4 (e2m1) matrix-core tiles on every CU, with unit
     and random E8M0 block scales, checked exactly; then the dense fp8 and fp4 rates."""
     return json.loads(native().diag_mfma_lowp(device, waves_per_cu, iters, seed))
+
+
+def lds(device=0, wgs_per_cu=4, rate_iters=8192, seed=0x5EED):
+    """Every CU's Local Data Share: `wgs_per_cu` workgroups per CU each write and verify all 160 KiB
+    twice (a hash pattern, then its inverse), binned by the CU they ran on; then `rate_iters`
+    sweeps of 16-byte reads over the array on every CU for the aggregate read rate."""
+    return json.loads(native().diag_lds(device, wgs_per_cu, rate_iters, seed))
 
 
 def gemm_check(device=0, m=4096, n=4096, k=4096, seed=0x5EED):
@@ -133,6 +142,16 @@ def mfma_lowp_planted(check_plants, rate_plants=(), device=0, waves_per_cu=1, it
     check = [(_LOWP_VARIANTS[p[0]],) + tuple(p[1:]) for p in check_plants]
     rate = [(_LOWP_FORMATS[p[0]],) + tuple(p[1:]) for p in rate_plants]
     return json.loads(native().diag_mfma_lowp_planted(device, waves_per_cu, iters, seed, check, rate))
+
+
+LDS_WORDS = 40960  # 32-bit words of a CU's Local Data Share
+
+
+def lds_planted(plants, device=0, wgs_per_cu=1, rate_iters=64, seed=0x5EED):
+    """`plants` = [(workgroup or ALL_WAVES, pass, word, xor mask), ...]: thread 0 of that march
+    workgroup XORs the mask into that word of its LDS after the pass's fill and before its verify.
+    The rate phase takes no plant."""
+    return json.loads(native().diag_lds_planted(device, wgs_per_cu, rate_iters, seed, list(plants)))
 
 
 MAX_DELAY_TICKS = 10_000_000  # 100 ms of the 100 MHz constant clock
@@ -198,6 +217,12 @@ def mfma_tile(path, tile, scaled=False, device=0, seed=0x5EED):
     record array of TILE_LANE (fragment dwords a and b, scale exponents ea and eb, the matrix
     core's acc and the check's expect)."""
     return np.frombuffer(native().diag_mfma_tile(device, TILE_PATHS[path], int(scaled), seed, tile), dtype=TILE_LANE)
+
+
+def lds_data(wg, pass_, grid, device=0, seed=0x5EED):
+    """The LDS_WORDS words that workgroup `wg` of a march of `grid` workgroups holds after pass
+    `pass_` (0: the pattern, 1: its inverse), as uint32."""
+    return np.frombuffer(native().diag_lds_data(device, seed, wg, pass_, grid), dtype="<u4")
 
 
 def _bf16_bytes(x):

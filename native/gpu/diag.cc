@@ -154,6 +154,30 @@ json::Value to_json(int device, const bgc_lowp_result& r) {
                               {"passed", mism == 0 && r.throughput_ok != 0}});
 }
 
+json::Value to_json(int device, const bgc_lds_result& r) {
+  json::Value bad = json::Value::array();
+  for (int i = 0; i < r.bad_cus && i < 64; ++i) bad.push_back(r.bad_cu_keys[i]);
+  char bits[16];
+  std::snprintf(bits, sizeof(bits), "0x%08x", r.bad_bits);
+  const bool clean = r.mismatches == 0;
+  return json::Value::object({{"device", device},
+                              {"cus", r.cus},
+                              {"cus_seen", r.cus_seen},
+                              {"bad_cus", r.bad_cus},
+                              {"bad_cu_keys", bad},
+                              {"words_checked", static_cast<unsigned long long>(r.words_checked)},
+                              {"mismatches", static_cast<unsigned long long>(r.mismatches)},
+                              {"first_bad_cu_key", clean ? json::Value() : json::Value(r.first_bad_cu_key)},
+                              {"first_bad_word", clean ? json::Value() : json::Value(static_cast<unsigned long long>(r.first_bad_word))},
+                              {"bad_bits", clean ? json::Value() : json::Value(std::string(bits))},
+                              {"read_tbps", r.read_tbps},
+                              {"rate_ok", r.rate_ok != 0},
+                              {"slowest_cu_key", r.slowest_cu_key},
+                              {"cu_balance", r.cu_balance},
+                              {"elapsed_ms", r.elapsed_ms},
+                              {"passed", clean && r.rate_ok != 0}});
+}
+
 json::Value to_json(int device, const bgc_pcie_result& r) {
   return json::Value::object({{"device", device}, {"bytes", static_cast<unsigned long long>(r.bytes)},
                               {"iters", r.iters}, {"h2d_gbps", r.h2d_gbps}, {"d2h_gbps", r.d2h_gbps},
@@ -205,6 +229,10 @@ json::Value Diag::mfma(int device, int waves_per_cu, int throughput_iters, uint3
 
 json::Value Diag::mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint32_t seed) {
   return call("low-precision mfma diag", lowp_, device, waves_per_cu, throughput_iters, seed);
+}
+
+json::Value Diag::lds(int device, int wgs_per_cu, int rate_iters, uint32_t seed) {
+  return call("lds diag", lds_, device, wgs_per_cu, rate_iters, seed);
 }
 
 json::Value Diag::pcie(int device, uint64_t bytes, int iters, uint32_t seed) {
@@ -344,6 +372,12 @@ DiagFloors DiagFloors::mi355x_defaults() {
   // the clocks are, against ~5 and ~10 PF/s dense peaks
   f.min_fp8_tflops = 3000;
   f.min_fp4_tflops = 5000;
+  // LDS (4 march workgroups per CU, then 8192 sweeps of 512-thread 16-byte reads, right after the
+  // MFMA check; profiles/lds_diag/lds_rate.json): 121-138 TB/s over 12 runs back to back, rising as
+  // the clocks warm, and 116-120 TB/s in whole passes in a fresh worker process, against ~150 TB/s
+  // at 2.4 GHz; the march reached 256 of 256 CUs in every run
+  f.min_lds_read_tbps = 85;
+  f.min_lds_cu_coverage = 1.0;
   // burn-in: measured on MI355X in profiles/archive/diag_burn_r2.json (sustained bf16 MFMA at
   // 97 % of the 2.5 PF/s dense peak once clocks settle)
   f.min_burn_tflops = 1800;  // measured 2409-2421 PF/s mean over 10 s at 1.17-1.22 kW, 2.34-2.39 GHz
@@ -376,6 +410,7 @@ const std::vector<std::pair<std::string, DiagFloors::Field>>& DiagFloors::fields
   static const std::vector<std::pair<std::string, Field>> table = {
       BGC_FLOOR(min_read_gbps), BGC_FLOOR(min_copy_gbps), BGC_FLOOR(min_write_gbps), BGC_FLOOR(min_mfma_tflops),
       BGC_FLOOR(min_xcc_balance), BGC_FLOOR(min_fp8_tflops), BGC_FLOOR(min_fp4_tflops), BGC_FLOOR(min_xccs),
+      BGC_FLOOR(min_lds_read_tbps), BGC_FLOOR(min_lds_cu_coverage),
       BGC_FLOOR(min_burn_tflops), BGC_FLOOR(min_burn_sustain), BGC_FLOOR(max_burn_hotspot_c),
       BGC_FLOOR(max_burn_thermal_violation_pct), BGC_FLOOR(min_pcie_h2d_gbps), BGC_FLOOR(min_pcie_d2h_gbps),
       BGC_FLOOR(require_full_pcie_width), BGC_FLOOR(min_pcie_speed_fraction), BGC_FLOOR(min_soak_tflops),
@@ -441,6 +476,21 @@ json::Value judge_diag(const json::Value& result, const DiagFloors& fl) {
     floor_check(lp, "fp8_tflops", fl.min_fp8_tflops, "MX fp8 MFMA TFLOP/s");
     floor_check(lp, "fp4_tflops", fl.min_fp4_tflops, "MX fp4 MFMA TFLOP/s");
   }
+  const json::Value& lds = result.get("lds");
+  if (lds.is_object()) {
+    if (num(lds, "mismatches") > 0) {
+      fail("LDS march mismatches on %d CU(s): %.0f words (first on CU key %d at word %d, bits %s)",
+           static_cast<int>(num(lds, "bad_cus")), num(lds, "mismatches"), static_cast<int>(num(lds, "first_bad_cu_key")),
+           static_cast<int>(num(lds, "first_bad_word")), lds.get_string("bad_bits", "?").c_str());
+    }
+    if (lds.get("rate_ok").is_bool() && !lds.get("rate_ok").as_bool()) failures.push_back("LDS rate phase read wrong data");
+    if (fl.min_lds_read_tbps > 0 && num(lds, "read_tbps") < fl.min_lds_read_tbps) {
+      fail("LDS read TB/s %.1f below floor %.1f", num(lds, "read_tbps"), fl.min_lds_read_tbps);
+    }
+    if (fl.min_lds_cu_coverage > 0 && num(lds, "cus") > 0 && num(lds, "cus_seen") < fl.min_lds_cu_coverage * num(lds, "cus")) {
+      fail("LDS march reached %d of %d CUs", static_cast<int>(num(lds, "cus_seen")), static_cast<int>(num(lds, "cus")));
+    }
+  }
   const json::Value& burn = result.get("burn");
   if (burn.is_object()) {
     if (num(burn, "mismatches") > 0) failures.push_back("burn-in MFMA accumulators wrong");
@@ -497,7 +547,7 @@ json::Value judge_diag(const json::Value& result, const DiagFloors& fl) {
   if (result.get("error").is_string()) failures.push_back(result.get_string("error"));
   // a section that failed to run (a HIP fault, a worker that timed out) carries the cause
   // as {"error": ...}: that is a failure in its own right, whatever the floors say
-  static const char* const kSections[] = {"hbm", "hbm_walk", "mfma", "lowp", "burn", "pcie", "soak", "gemm"};
+  static const char* const kSections[] = {"hbm", "hbm_walk", "mfma", "lowp", "lds", "burn", "pcie", "soak", "gemm"};
   for (const char* sect : kSections) {
     const json::Value& v = result.get(sect);
     if (v.is_object() && v.get("error").is_string()) failures.push_back(std::string(sect) + ": " + v.get_string("error"));

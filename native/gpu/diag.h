@@ -29,6 +29,11 @@ struct DiagFloors {
   double min_fp8_tflops = 0;
   double min_fp4_tflops = 0;
   int min_xccs = 0;            // XCCs that must have run MFMA work
+  // Local Data Share (`lds` section): any word of the per-CU march that reads back wrong fails; rate
+  // floor on the aggregate LDS read rate, and the share of the device's CUs (cus_seen / cus) that a
+  // march workgroup must have run on.
+  double min_lds_read_tbps = 0;
+  double min_lds_cu_coverage = 0;
   // Burn-in (sustained MFMA load, `burn` section): rate floor, the rate may not sag
   // below this fraction of its first launch, and the thermal limits under load.
   double min_burn_tflops = 0;
@@ -79,6 +84,7 @@ json::Value judge_diag(const json::Value& result, const DiagFloors& floors);
 json::Value to_json(int device, const bgc_hbm_result& r);
 json::Value to_json(int device, const bgc_mfma_result& r);
 json::Value to_json(int device, const bgc_lowp_result& r);
+json::Value to_json(int device, const bgc_lds_result& r);
 json::Value to_json(int device, const bgc_pcie_result& r);
 json::Value to_json(int device, const bgc_soak_result& r);
 json::Value to_json(int device, const bgc_hbm_walk_result& r);
@@ -96,6 +102,8 @@ class Diag {
   json::Value mfma(int device, int waves_per_cu, int throughput_iters, uint32_t seed);
   // MX block-scaled fp8 / fp4 matrix-core tiles and rates (see bgc_diag_mfma_lowp).
   json::Value mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint32_t seed);
+  // March test of every CU's whole LDS and the LDS read rate (see bgc_diag_lds).
+  json::Value lds(int device, int wgs_per_cu, int rate_iters, uint32_t seed);
   // MFMA GEMM on the device vs a host fp32 product of the same bf16 operands
   // (deterministic pseudo-random values in [-1, 1]).  Returns max error and the bound.
   json::Value gemm_check(int device, int m, int n, int k, uint32_t seed);
@@ -152,6 +160,7 @@ class Diag {
   BGC_DIAG_ENTRY(pcie_, bgc_diag_pcie);
   BGC_DIAG_ENTRY(mfma_, bgc_diag_mfma);
   BGC_DIAG_ENTRY(lowp_, bgc_diag_mfma_lowp);
+  BGC_DIAG_ENTRY(lds_, bgc_diag_lds);
   BGC_DIAG_ENTRY(burn_, bgc_diag_burn_dtype);
   BGC_DIAG_ENTRY(soak_, bgc_diag_gemm_soak);
   BGC_DIAG_ENTRY(gemm_, bgc_diag_gemm);

@@ -93,6 +93,9 @@ class FileLock {
   int fd_ = -1;
 };
 
+// Sweeps of the LDS rate phase: 2.4-2.9 ms on the MI355X (profiles/lds_diag/lds_rate.json)
+constexpr int kLdsRateIters = 8192;
+
 class HipDiagEngine : public DiagEngine {
  public:
   explicit HipDiagEngine(std::string pcie_lock_path = "") : pcie_lock_path_(std::move(pcie_lock_path)) {}
@@ -121,6 +124,10 @@ class HipDiagEngine : public DiagEngine {
     if (plan.lowp) {
       r["lowp"] = d.mfma_lowp(dev, 32, 4096, seed);  // ~5 ms
       lap("lowp");
+    }
+    if (plan.lds) {
+      r["lds"] = d.lds(dev, 4, kLdsRateIters, seed);
+      lap("lds");
     }
     r["gemm"] = d.gemm_check(dev, 64, 64, 512, seed);
     lap("gemm");
@@ -290,6 +297,10 @@ class ScriptedDiagEngine : public DiagEngine {
       r["lowp"] = Value::object({{"device", dev}, {"fp8_tflops", 4000.0}, {"fp4_tflops", 7000.0}, {"mismatches", 0},
                                  {"bad_cus", 0}, {"throughput_ok", true}, {"passed", true}});
     }
+    if (plan.lds) {
+      r["lds"] = Value::object({{"device", dev}, {"cus", 256}, {"cus_seen", 256}, {"bad_cus", 0}, {"mismatches", 0},
+                                {"read_tbps", 100.0}, {"rate_ok", true}, {"cu_balance", 0.97}, {"passed", true}});
+    }
     r["gemm"] = Value::object({{"passed", true}});
     if (plan.soak_launches > 0) {
       r["soak"] = Value::object({{"tflops_mean", 1300.0}, {"row_mismatches", 0}, {"col_mismatches", 0}, {"passed", true}});
@@ -342,6 +353,7 @@ Value to_json(const DiagPlan& p) {
                         {"soak_size", p.soak_size},
                         {"soak_launches", p.soak_launches},
                         {"lowp", p.lowp},
+                        {"lds", p.lds},
                         {"burn_ms", p.burn_ms},
                         {"burn_dtype", burn_dtype_name(p.burn_dtype)}});
 }
@@ -358,6 +370,7 @@ DiagPlan diag_plan_from_json(const Value& v) {
   p.soak_size = i32("soak_size", p.soak_size);
   p.soak_launches = i32("soak_launches", p.soak_launches);
   p.lowp = v.get("lowp").is_bool() ? v.get("lowp").as_bool() : p.lowp;
+  p.lds = v.get("lds").is_bool() ? v.get("lds").as_bool() : p.lds;
   p.burn_ms = i32("burn_ms", p.burn_ms);
   if (v.get("burn_dtype").is_string()) p.burn_dtype = burn_dtype_code(v.get_string("burn_dtype"));
   return p;

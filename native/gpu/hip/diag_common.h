@@ -1,5 +1,5 @@
-// Shared by the diagnostics' sources (gpu_diag.hip, hbm.hip, mfma.hip, gemm_soak.hip): vector
-// types, the hash, the last-error string and the host helpers every entry point uses.
+// Shared by the diagnostics' sources (gpu_diag.hip, hbm.hip, mfma.hip, lds.hip, gemm_soak.hip): vector
+// types, the hash, the CU a wave runs on, the last-error string and the host helpers every entry point uses.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -30,7 +30,18 @@ __host__ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   return x;
 }
 
-#define HIP_TRY(expr)                                                                   \
+// The physical CU a wave runs on: xcc << 8 | se << 5 | sh << 4 | cu, below BGC_DIAG_MAX_CU_KEYS.
+__device__ __forceinline__ uint32_t cu_key() {
+  uint32_t xcc, hwid;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+  uint32_t cu = (hwid >> 8) & 0xF;
+  uint32_t sh = (hwid >> 12) & 0x1;
+  uint32_t se = (hwid >> 13) & 0x7;
+  return ((xcc & 0x7) << 8) | (se << 5) | (sh << 4) | cu;
+}
+
+#define HIP_TRY(expr)                                                                  \
   do {                                                                                  \
     hipError_t _e = (expr);                                                             \
     if (_e != hipSuccess) {                                                             \

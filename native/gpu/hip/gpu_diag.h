@@ -15,7 +15,7 @@
 extern "C" {
 #endif
 
-#define BGC_DIAG_ABI_VERSION 14
+#define BGC_DIAG_ABI_VERSION 15
 #define BGC_DIAG_MAX_CU_KEYS 2048
 
 // The data the diagnostics generate for themselves.  All arithmetic is modulo 2^32 (mix32) or
@@ -57,6 +57,13 @@ extern "C" {
 //    element j of 8; fp8, K 16 g .. 16 g + 15 in bytes 0..15 and K 64 + 16 g .. in bytes 16..31; fp4,
 //    K 32 g .. 32 g + 31 in 16 bytes, the even k in the low nibble; the scale byte of (rc, block g).
 //    The result lane l holds C[4 g + i][rc] in accumulator element i.
+//  * LDS march and rate (bgc_diag_lds).  A workgroup holds its CU's whole LDS as BGC_LDS_WORDS 32-bit
+//    words.  For workgroup b of a launch, s_b = mix32(seed + (b + 1) * 0x9e3779b9); word j holds
+//    P(b, j) = mix32(j ^ s_b) in pass 0 and ~P(b, j) in pass 1; the rate phase reads P.  mix32 is a
+//    bijection, so the words of a workgroup are pairwise distinct, and the s_b of one launch are
+//    pairwise distinct, so no word equals the same word of any other workgroup: a write that lands
+//    at the wrong address reads back as a wrong value elsewhere, what the previous workgroup left on
+//    the CU cannot pass, and every cell is checked holding both 0 and 1.
 
 typedef struct {
   uint64_t bytes;          // buffer size tested
@@ -200,6 +207,30 @@ typedef struct {
 // so every cell is checked holding both 0 and 1.  Stops early after `budget_ms`.
 int bgc_diag_hbm_walk(int device, double fraction, uint64_t chunk_bytes, int budget_ms, uint32_t seed,
                       bgc_hbm_walk_result* out);
+#define BGC_LDS_WORDS 40960  // 163840 B: all of a CU's Local Data Share
+typedef struct {
+  int cus;                  // CUs of the device
+  int cus_seen;             // distinct CUs that ran a march workgroup
+  int bad_cus;
+  uint64_t words_checked;   // 2 * BGC_LDS_WORDS per workgroup
+  uint64_t mismatches;      // 32-bit words that read back wrong, both passes
+  int first_bad_cu_key;     // lowest bad CU key, -1 if none
+  uint32_t first_bad_word;  // lowest failing word index on that CU
+  uint32_t bad_bits;        // OR of expected ^ found over all failures
+  double read_tbps;         // rate phase: bytes read from LDS / device time, all CUs
+  int rate_ok;              // every thread's sum matched
+  int slowest_cu_key;       // CU whose rate workgroup took longest (constant clock), -1 if none ran
+  double cu_balance;        // fastest / slowest CU time of the rate phase (1.0 = balanced)
+  double elapsed_ms;
+  int bad_cu_keys[64];
+} bgc_lds_result;
+
+// Every CU's Local Data Share, which the other checks never cover as a whole: a march of all
+// 160 KiB per CU by `wgs_per_cu` (1..64) workgroups per CU, each of which fills the whole array and
+// so is alone on its CU (16-byte stores, then the inverse as strided dword stores; verified with
+// 16- and 8-byte loads), attributed to (XCC, SE, SH, CU); then `rate_iters` (1..65536) sweeps of
+// conflict-free 16-byte reads over the array by one workgroup per CU, for the LDS read rate.
+int bgc_diag_lds(int device, int wgs_per_cu, int rate_iters, uint32_t seed, bgc_lds_result* out);
 // ---------------------------------------------------------------------------------------------
 // Planted variants: FOR TESTS ONLY.  Each runs the same implementation as the entry point it is
 // named after, with a list of deliberately wrong values ("plants") written into the diagnostic's
@@ -313,6 +344,18 @@ typedef struct {
 int bgc_diag_gemm_soak_planted(int device, int m, int n, int k, int launches, uint32_t seed,
                                const bgc_soak_plant* plants, int n_plants, bgc_soak_result* out);
 
+// lds[word] ^= xor_mask in march workgroup `wg` (or in every one, BGC_PLANT_ALL_WAVES), by its thread 0
+// after pass `pass`'s fill and before its verify.  pass 0 or 1, word < BGC_LDS_WORDS, a non-zero
+// mask, wg below the march's grid (CUs * wgs_per_cu).  The rate phase takes no plant.
+typedef struct {
+  int wg;
+  int pass;
+  uint32_t word;
+  uint32_t xor_mask;
+} bgc_lds_plant;
+int bgc_diag_lds_planted(int device, int wgs_per_cu, int rate_iters, uint32_t seed, const bgc_lds_plant* plants, int n,
+                         bgc_lds_result* out);
+
 // ---------------------------------------------------------------------------------------------
 // Generated data: FOR TESTS ONLY, never loaded by the node agent or the diag worker.  Each runs
 // the same implementation as the entry point it is named after and then copies the data that
@@ -356,6 +399,9 @@ typedef struct {
 // `tile` of matrix-core path `path` (BGC_TILE_*), with block scales if `scaled` (MX paths only),
 // and every lane writes what it holds to lanes[0..63].
 int bgc_diag_mfma_tile(int device, int path, int scaled, uint32_t seed, uint32_t tile, bgc_tile_lane* lanes);
+// The march with `grid` (1..4096) workgroups; workgroup `wg` (< grid) copies its whole array, as it
+// is after pass `pass`'s (0 or 1) verify, to `data` (BGC_LDS_WORDS words).
+int bgc_diag_lds_data(int device, uint32_t seed, int wg, int pass, int grid, void* data);
 
 // PCI bus id of a HIP device ("0000:05:00.0", lower-case hex) — the key the node agent and
 // the RCCL probe use to match a HIP device (renumbered inside a container) to amdsmi.

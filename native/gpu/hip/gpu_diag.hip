@@ -5,6 +5,7 @@
 //    the pinned host<->device copies for PCIe;
 //  * mfma.hip: the per-CU bf16 and MX fp8/fp4 matrix-core checks and throughput kernels, the
 //    burn-in loop that runs them back to back, and the one-wave GEMMs on caller operands;
+//  * lds.hip: the per-CU march test of the whole Local Data Share and its read rate;
 //  * gemm_soak.hip: the ABFT-checked LDS-tiled GEMMs (gemm_soak and the 8-phase gemm_pingpong).
 // The design notes in those files follow the CDNA4 guides (cdna_hip_programming.md,
 // MI355X_MICROARCH.md).

@@ -39,16 +39,6 @@ __device__ __forceinline__ int operand(uint32_t seed, uint32_t tile, int r, int 
   return static_cast<int>(h % 3u) - 1;
 }
 
-__device__ __forceinline__ uint32_t cu_key() {
-  uint32_t xcc, hwid;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-  uint32_t cu = (hwid >> 8) & 0xF;
-  uint32_t sh = (hwid >> 12) & 0x1;
-  uint32_t se = (hwid >> 13) & 0x7;
-  return ((xcc & 0x7) << 8) | (se << 5) | (sh << 4) | cu;
-}
-
 // ---------------------------------------------------------------------------
 // Tile traits: a 16x16xkK MFMA on hash-derived operands.  Lane l holds its part of A row
 // (l & 15) and of B column (l & 15) from lane group l >> 4; the result lane l holds column

@@ -232,6 +232,9 @@ void register_gpu(py::module_& m) {
   m.def("diag_mfma_lowp", [](int device, int waves_per_cu, int iters, unsigned seed) {
     return dump_nogil([&] { return Diag::instance().mfma_lowp(device, waves_per_cu, iters, seed); });
   }, py::arg("device"), py::arg("waves_per_cu") = 32, py::arg("iters") = 4096, py::arg("seed") = 0x5eed);
+  m.def("diag_lds", [](int device, int wgs_per_cu, int rate_iters, unsigned seed) {
+    return dump_nogil([&] { return Diag::instance().lds(device, wgs_per_cu, rate_iters, seed); });
+  }, py::arg("device"), py::arg("wgs_per_cu") = 4, py::arg("rate_iters") = 8192, py::arg("seed") = 0x5eed);
   m.def("diag_gemm", [](int device, int mm, int nn, int kk, const std::string& a, const std::string& b) {
     if (a.size() != static_cast<size_t>(mm) * kk * 2 || b.size() != static_cast<size_t>(kk) * nn * 2) {
       throw std::invalid_argument("A must be M*K and B K*N bf16 values");
@@ -325,6 +328,12 @@ void register_gpu(py::module_& m) {
                    c.data(), count(c), r.data(), count(r));
   }, py::arg("device"), py::arg("waves_per_cu"), py::arg("iters"), py::arg("seed"), py::arg("check_plants"),
      py::arg("rate_plants"));
+  m.def("diag_lds_planted", [](int device, int wgs_per_cu, int rate_iters, unsigned seed,
+                               const std::vector<std::tuple<int, int, unsigned, unsigned>>& plants) {
+    std::vector<bgc_lds_plant> p;
+    for (const auto& [wg, pass, word, mask] : plants) p.push_back({wg, pass, word, mask});
+    return planted("lds diag", BGC_DIAG_ENTRY(bgc_diag_lds_planted), device, wgs_per_cu, rate_iters, seed, p.data(), count(p));
+  }, py::arg("device"), py::arg("wgs_per_cu"), py::arg("rate_iters"), py::arg("seed"), py::arg("plants"));
   // Delay plants: (wave or -1, ticks of the constant clock) in the timed throughput launch; and a burn
   // whose launches from `first_delayed_launch` on have every wave delayed by `ticks`.
   m.def("diag_mfma_delayed", [](int device, int waves_per_cu, int iters, unsigned seed,
@@ -397,6 +406,15 @@ void register_gpu(py::module_& m) {
     }
     return py::bytes(lanes);
   }, py::arg("device"), py::arg("path"), py::arg("scaled"), py::arg("seed"), py::arg("tile"));
+  // the BGC_LDS_WORDS words of one march workgroup, as bytes
+  m.def("diag_lds_data", [](int device, unsigned seed, int wg, int pass, int grid) {
+    std::string data(4 * BGC_LDS_WORDS, '\0');
+    {
+      py::gil_scoped_release nogil;
+      Diag::instance().check("lds diag", BGC_DIAG_ENTRY(bgc_diag_lds_data)(device, seed, wg, pass, grid, static_cast<void*>(data.data())));
+    }
+    return py::bytes(data);
+  }, py::arg("device"), py::arg("seed"), py::arg("wg"), py::arg("pass"), py::arg("grid"));
 #undef BGC_DIAG_ENTRY
   m.def("pcie_check", [](std::shared_ptr<PyBackend> b, int index, int hip_device, unsigned long long bytes, unsigned seed) {
     return dump_nogil([&] {

@@ -26,6 +26,7 @@ for name, fn in (("hbm", lambda: ops.hbm(0, nbytes=1 << 30)),
                  ("hbm_walk", lambda: ops.hbm_walk(0)),
                  ("mfma", lambda: ops.mfma(0)),
                  ("mfma_lowp", lambda: ops.mfma_lowp(0)),
+                 ("lds", lambda: ops.lds(0)),
                  ("gemm_check", lambda: ops.gemm_check(0, 1024, 1024, 1024)),
                  ("gemm_soak", lambda: ops.gemm_soak(0, 8192, 8192, 8192, launches=20)),
                  ("pcie", lambda: ops.pcie(0)),
