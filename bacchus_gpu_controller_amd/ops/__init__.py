@@ -10,6 +10,8 @@ These are the only compute kernels in the framework: the reference controller ha
 * ``mfma(device)``      — exact-integer bf16 MFMA tiles on every CU + a throughput pass
 * ``mfma_lowp(device)`` — the same for the MX block-scaled fp8 / fp4 matrix-core path
   (``v_mfma_scale_f32_16x16x128_f8f6f4``), with and without E8M0 block scales
+* ``mfma_classic(device)`` — the same for the fp16, int8, fp32-input and fp64 matrix-core paths, with
+  operands as wide as each path's multipliers
 * ``lds(device)``       — a march test of every CU's whole Local Data Share (160 KiB), attributed to
   the CU, then the aggregate LDS read rate
 * ``gemm_check(device)``— a bf16 GEMM on the matrix cores checked element by element against
@@ -26,11 +28,11 @@ These are the only compute kernels in the framework: the reference controller ha
 * ``pcie(device)``      — host<->device copy bandwidth, pinned
 * ``device_bdf(device)``— the HIP device's PCI address, to match it to amdsmi / kubelet
 * ``hbm_planted``, ``hbm_walk_planted``, ``pcie_planted``, ``mfma_planted``,
-  ``mfma_lowp_planted``, ``lds_planted``, ``gemm_soak_planted`` — for tests: the same diagnostics with wrong
+  ``mfma_lowp_planted``, ``mfma_classic_planted``, ``lds_planted``, ``gemm_soak_planted`` — for tests: the same diagnostics with wrong
   values planted in their own data, to show that they are detected (see below)
 * ``mfma_delayed``, ``burn_delayed`` — for tests: the matrix-core throughput and the burn with
   chosen waves or launches made slow by a known time, to show that it reaches the rates
-* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile``, ``lds_data`` — for tests:
+* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile``, ``mfma_classic_tile``, ``lds_data`` — for tests:
   the same diagnostics, returning the data they generated for themselves (see below)
 
 All fail loudly (RuntimeError) if ``libbgc_gpu_diag.so`` or the GPU is missing; there
@@ -75,6 +77,24 @@ def mfma_lowp(device=0, waves_per_cu=32, iters=4096, seed=0x5EED):
     """MX block-scaled fp8 (e4m3) and fp4 (e2m1) matrix-core tiles on every CU, with unit
     and random E8M0 block scales, checked exactly; then the dense fp8 and fp4 rates."""
     return json.loads(native().diag_mfma_lowp(device, waves_per_cu, iters, seed))
+
+
+CLASSIC_PATHS = {"fp16": 0, "int8": 1, "fp32": 2, "fp64": 3}  # BGC_CLASSIC_*: the order of every per-path list
+CLASSIC_K = {"fp16": 32, "int8": 64, "fp32": 4, "fp64": 4}
+CLASSIC_DTYPES = {"fp16": np.float16, "int8": np.int8, "fp32": np.float32, "fp64": np.float64}
+CLASSIC_CHECK_ROUNDS = 4  # BGC_CLASSIC_CHECK_ROUNDS
+
+
+def _classic_path(path):
+    """a path's name, or its number as it is (so a test can pass one out of range)"""
+    return CLASSIC_PATHS.get(path, path) if isinstance(path, str) else path
+
+
+def mfma_classic(device=0, waves_per_cu=32, iters=8192, seed=0x5EED):
+    """The fp16, int8, fp32-input and fp64 matrix cores: exact tiles with full-width operands on every
+    CU, then each path's dense rate (``fp16_tflops``, ``int8_tops``, ``fp32_tflops``, ``fp64_tflops``;
+    ``rate_ms`` in that order)."""
+    return json.loads(native().diag_mfma_classic(device, waves_per_cu, iters, seed))
 
 
 def lds(device=0, wgs_per_cu=4, rate_iters=8192, seed=0x5EED):
@@ -142,6 +162,15 @@ def mfma_lowp_planted(check_plants, rate_plants=(), device=0, waves_per_cu=1, it
     check = [(_LOWP_VARIANTS[p[0]],) + tuple(p[1:]) for p in check_plants]
     rate = [(_LOWP_FORMATS[p[0]],) + tuple(p[1:]) for p in rate_plants]
     return json.loads(native().diag_mfma_lowp_planted(device, waves_per_cu, iters, seed, check, rate))
+
+
+def mfma_classic_planted(check_plants, rate_plants=(), device=0, waves_per_cu=1, iters=64, seed=0x5EED):
+    """As mfma_planted, with the path ("fp16", "int8", "fp32", "fp64", or its number) in front of
+    every plant.  The delta is converted to the path's accumulator type; an int8 delta must be an
+    integer below 2^31 in magnitude."""
+    check = [(_classic_path(p[0]),) + tuple(p[1:]) for p in check_plants]
+    rate = [(_classic_path(p[0]),) + tuple(p[1:]) for p in rate_plants]
+    return json.loads(native().diag_mfma_classic_planted(device, waves_per_cu, iters, seed, check, rate))
 
 
 LDS_WORDS = 40960  # 32-bit words of a CU's Local Data Share
@@ -219,6 +248,16 @@ def mfma_tile(path, tile, scaled=False, device=0, seed=0x5EED):
     return np.frombuffer(native().diag_mfma_tile(device, TILE_PATHS[path], int(scaled), seed, tile), dtype=TILE_LANE)
 
 
+CLASSIC_TILE_LANE = np.dtype([("a", "<u4", 4), ("b", "<u4", 4), ("acc", "<f8", 4), ("expect", "<f8", 4)])
+
+
+def mfma_classic_tile(path, tile, device=0, seed=0x5EED):
+    """What each of the 64 lanes holds for check tile `tile` of the "fp16", "int8", "fp32" or "fp64"
+    path: a record array of CLASSIC_TILE_LANE (fragment dwords a and b, the matrix core's acc and
+    the check's expect, both as doubles)."""
+    return np.frombuffer(native().diag_mfma_classic_tile(device, _classic_path(path), seed, tile), dtype=CLASSIC_TILE_LANE)
+
+
 def lds_data(wg, pass_, grid, device=0, seed=0x5EED):
     """The LDS_WORDS words that workgroup `wg` of a march of `grid` workgroups holds after pass
     `pass_` (0: the pattern, 1: its inverse), as uint32."""
@@ -247,6 +286,21 @@ def gemm(a, b, device=0):
         raise ValueError(f"inner dimensions differ: A is {m}x{k}, B is {k2}x{n}")
     c = native().diag_gemm(device, m, n, k, _bf16_bytes(a), _bf16_bytes(b))
     return np.frombuffer(c, dtype=np.float32).reshape(m, n)
+
+
+def gemm_dtype(a, b, path, device=0):
+    """C = A @ B on classic path `path` ("fp16", "int8", "fp32", "fp64"), one wave per 16x16 tile
+    (classic_gemm).  A is MxK, B is KxN, converted to the path's element type; M and N must be
+    multiples of 16 (up to 4096) and K of the path's K (up to 8192).  Returns a float64 numpy array
+    MxN, which holds every path's results exactly."""
+    m, k = a.shape
+    k2, n = b.shape
+    if k != k2:
+        raise ValueError(f"inner dimensions differ: A is {m}x{k}, B is {k2}x{n}")
+    dt = CLASSIC_DTYPES[path]
+    c = native().diag_gemm_dtype(device, CLASSIC_PATHS[path], m, n, k, np.ascontiguousarray(a, dtype=dt).tobytes(),
+                                 np.ascontiguousarray(b, dtype=dt).tobytes())
+    return np.frombuffer(c, dtype=np.float64).reshape(m, n)
 
 
 def gemm_tiled(a, bt, device=0):

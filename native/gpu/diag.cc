@@ -154,6 +154,32 @@ json::Value to_json(int device, const bgc_lowp_result& r) {
                               {"passed", mism == 0 && r.throughput_ok != 0}});
 }
 
+json::Value to_json(int device, const bgc_classic_result& r) {
+  json::Value bad = json::Value::array();
+  for (int i = 0; i < r.bad_cus && i < 64; ++i) bad.push_back(r.bad_cu_keys[i]);
+  json::Value ms = json::Value::array();
+  for (int p = 0; p < 4; ++p) ms.push_back(r.rate_ms[p]);
+  const uint64_t mism = r.mismatches[0] + r.mismatches[1] + r.mismatches[2] + r.mismatches[3];
+  return json::Value::object({{"device", device},
+                              {"tiles_checked", static_cast<unsigned long long>(r.tiles_checked)},
+                              {"fp16_mismatches", static_cast<unsigned long long>(r.mismatches[BGC_CLASSIC_FP16])},
+                              {"int8_mismatches", static_cast<unsigned long long>(r.mismatches[BGC_CLASSIC_INT8])},
+                              {"fp32_mismatches", static_cast<unsigned long long>(r.mismatches[BGC_CLASSIC_FP32])},
+                              {"fp64_mismatches", static_cast<unsigned long long>(r.mismatches[BGC_CLASSIC_FP64])},
+                              {"mismatches", static_cast<unsigned long long>(mism)},
+                              {"cus_seen", r.cus_seen},
+                              {"bad_cus", r.bad_cus},
+                              {"bad_cu_keys", bad},
+                              {"fp16_tflops", r.rate[BGC_CLASSIC_FP16]},
+                              {"int8_tops", r.rate[BGC_CLASSIC_INT8]},
+                              {"fp32_tflops", r.rate[BGC_CLASSIC_FP32]},
+                              {"fp64_tflops", r.rate[BGC_CLASSIC_FP64]},
+                              {"rate_ms", ms},
+                              {"throughput_ok", r.throughput_ok != 0},
+                              {"elapsed_ms", r.elapsed_ms},
+                              {"passed", mism == 0 && r.throughput_ok != 0}});
+}
+
 json::Value to_json(int device, const bgc_lds_result& r) {
   json::Value bad = json::Value::array();
   for (int i = 0; i < r.bad_cus && i < 64; ++i) bad.push_back(r.bad_cu_keys[i]);
@@ -231,6 +257,10 @@ json::Value Diag::mfma_lowp(int device, int waves_per_cu, int throughput_iters, 
   return call("low-precision mfma diag", lowp_, device, waves_per_cu, throughput_iters, seed);
 }
 
+json::Value Diag::mfma_classic(int device, int waves_per_cu, int throughput_iters, uint32_t seed) {
+  return call("classic mfma diag", classic_, device, waves_per_cu, throughput_iters, seed);
+}
+
 json::Value Diag::lds(int device, int wgs_per_cu, int rate_iters, uint32_t seed) {
   return call("lds diag", lds_, device, wgs_per_cu, rate_iters, seed);
 }
@@ -270,6 +300,10 @@ void Diag::gemm(int device, int m, int n, int k, const uint16_t* a, const uint16
 
 void Diag::gemm_tiled(int device, int m, int n, int k, const uint16_t* a, const uint16_t* bt, float* c) {
   check("tiled gemm", tiled_(device, m, n, k, a, bt, c));
+}
+
+void Diag::gemm_dtype(int device, int path, int m, int n, int k, const void* a, const void* b, double* c) {
+  check("dtype gemm", gemm_dtype_(device, path, m, n, k, a, b, c));
 }
 
 void Diag::mx_gemm(int device, int fmt, int m, int n, int k, const uint8_t* a, const uint8_t* a_scales,
@@ -372,6 +406,14 @@ DiagFloors DiagFloors::mi355x_defaults() {
   // the clocks are, against ~5 and ~10 PF/s dense peaks
   f.min_fp8_tflops = 3000;
   f.min_fp4_tflops = 5000;
+  // fp16 / int8 / fp32 / fp64 MFMA (32 waves per CU x 8192 iterations, right after the MX check;
+  // profiles/mfma_classic/rates.json): over 12 runs back to back fp16 2177-2288 TF/s, int8 4204-4424
+  // TOP/s, fp32 155.8-157.5 and fp64 78.0-78.3 TF/s; in whole passes in a fresh process 2074-2090,
+  // 3902-3979, 146.4-148.2 and 77.2-77.7.  Each floor is 25 % under the lowest run of its path.
+  f.min_fp16_tflops = 1550;
+  f.min_int8_tops = 2900;
+  f.min_fp32_tflops = 109;
+  f.min_fp64_tflops = 57;
   // LDS (4 march workgroups per CU, then 8192 sweeps of 512-thread 16-byte reads, right after the
   // MFMA check; profiles/lds_diag/lds_rate.json): 121-138 TB/s over 12 runs back to back, rising as
   // the clocks warm, and 116-120 TB/s in whole passes in a fresh worker process, against ~150 TB/s
@@ -410,6 +452,7 @@ const std::vector<std::pair<std::string, DiagFloors::Field>>& DiagFloors::fields
   static const std::vector<std::pair<std::string, Field>> table = {
       BGC_FLOOR(min_read_gbps), BGC_FLOOR(min_copy_gbps), BGC_FLOOR(min_write_gbps), BGC_FLOOR(min_mfma_tflops),
       BGC_FLOOR(min_xcc_balance), BGC_FLOOR(min_fp8_tflops), BGC_FLOOR(min_fp4_tflops), BGC_FLOOR(min_xccs),
+      BGC_FLOOR(min_fp16_tflops), BGC_FLOOR(min_int8_tops), BGC_FLOOR(min_fp32_tflops), BGC_FLOOR(min_fp64_tflops),
       BGC_FLOOR(min_lds_read_tbps), BGC_FLOOR(min_lds_cu_coverage),
       BGC_FLOOR(min_burn_tflops), BGC_FLOOR(min_burn_sustain), BGC_FLOOR(max_burn_hotspot_c),
       BGC_FLOOR(max_burn_thermal_violation_pct), BGC_FLOOR(min_pcie_h2d_gbps), BGC_FLOOR(min_pcie_d2h_gbps),
@@ -475,6 +518,24 @@ json::Value judge_diag(const json::Value& result, const DiagFloors& fl) {
     }
     floor_check(lp, "fp8_tflops", fl.min_fp8_tflops, "MX fp8 MFMA TFLOP/s");
     floor_check(lp, "fp4_tflops", fl.min_fp4_tflops, "MX fp4 MFMA TFLOP/s");
+  }
+  const json::Value& cl = result.get("classic");
+  if (cl.is_object()) {
+    for (const char* path : {"fp16", "int8", "fp32", "fp64"}) {
+      const double bad = num(cl, (std::string(path) + "_mismatches").c_str());
+      if (bad > 0) {
+        const json::Value& keys = cl.get("bad_cu_keys");
+        const int first = keys.is_array() && !keys.items().empty() && keys.items()[0].is_number() ? static_cast<int>(keys.items()[0].as_double()) : -1;
+        fail("%s MFMA tile mismatches: %.0f elements, %d bad CU(s), first CU key %d", path, bad, static_cast<int>(num(cl, "bad_cus")), first);
+      }
+    }
+    if (cl.get("throughput_ok").is_bool() && !cl.get("throughput_ok").as_bool()) {
+      failures.push_back("fp16/int8/fp32/fp64 MFMA throughput accumulators wrong");
+    }
+    floor_check(cl, "fp16_tflops", fl.min_fp16_tflops, "fp16 MFMA TFLOP/s");
+    floor_check(cl, "int8_tops", fl.min_int8_tops, "int8 MFMA TOP/s");
+    floor_check(cl, "fp32_tflops", fl.min_fp32_tflops, "fp32 MFMA TFLOP/s");
+    floor_check(cl, "fp64_tflops", fl.min_fp64_tflops, "fp64 MFMA TFLOP/s");
   }
   const json::Value& lds = result.get("lds");
   if (lds.is_object()) {
@@ -547,7 +608,7 @@ json::Value judge_diag(const json::Value& result, const DiagFloors& fl) {
   if (result.get("error").is_string()) failures.push_back(result.get_string("error"));
   // a section that failed to run (a HIP fault, a worker that timed out) carries the cause
   // as {"error": ...}: that is a failure in its own right, whatever the floors say
-  static const char* const kSections[] = {"hbm", "hbm_walk", "mfma", "lowp", "lds", "burn", "pcie", "soak", "gemm"};
+  static const char* const kSections[] = {"hbm", "hbm_walk", "mfma", "lowp", "classic", "lds", "burn", "pcie", "soak", "gemm"};
   for (const char* sect : kSections) {
     const json::Value& v = result.get(sect);
     if (v.is_object() && v.get("error").is_string()) failures.push_back(std::string(sect) + ": " + v.get_string("error"));

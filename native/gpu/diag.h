@@ -29,6 +29,12 @@ struct DiagFloors {
   double min_fp8_tflops = 0;
   double min_fp4_tflops = 0;
   int min_xccs = 0;            // XCCs that must have run MFMA work
+  // fp16 / int8 / fp32 / fp64 matrix-core paths (`classic` section): any wrong tile element fails;
+  // rate floors on each path's dense MFMA rate (int8 in TOP/s).
+  double min_fp16_tflops = 0;
+  double min_int8_tops = 0;
+  double min_fp32_tflops = 0;
+  double min_fp64_tflops = 0;
   // Local Data Share (`lds` section): any word of the per-CU march that reads back wrong fails; rate
   // floor on the aggregate LDS read rate, and the share of the device's CUs (cus_seen / cus) that a
   // march workgroup must have run on.
@@ -84,6 +90,7 @@ json::Value judge_diag(const json::Value& result, const DiagFloors& floors);
 json::Value to_json(int device, const bgc_hbm_result& r);
 json::Value to_json(int device, const bgc_mfma_result& r);
 json::Value to_json(int device, const bgc_lowp_result& r);
+json::Value to_json(int device, const bgc_classic_result& r);
 json::Value to_json(int device, const bgc_lds_result& r);
 json::Value to_json(int device, const bgc_pcie_result& r);
 json::Value to_json(int device, const bgc_soak_result& r);
@@ -102,6 +109,8 @@ class Diag {
   json::Value mfma(int device, int waves_per_cu, int throughput_iters, uint32_t seed);
   // MX block-scaled fp8 / fp4 matrix-core tiles and rates (see bgc_diag_mfma_lowp).
   json::Value mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint32_t seed);
+  // fp16 / int8 / fp32 / fp64 matrix-core tiles and rates (see bgc_diag_mfma_classic).
+  json::Value mfma_classic(int device, int waves_per_cu, int throughput_iters, uint32_t seed);
   // March test of every CU's whole LDS and the LDS read rate (see bgc_diag_lds).
   json::Value lds(int device, int wgs_per_cu, int rate_iters, uint32_t seed);
   // MFMA GEMM on the device vs a host fp32 product of the same bf16 operands
@@ -120,6 +129,8 @@ class Diag {
   // MX fp8 (fmt 0) / fp4 (fmt 4) block-scaled GEMM on caller codes and E8M0 scales
   void mx_gemm(int device, int fmt, int m, int n, int k, const uint8_t* a, const uint8_t* a_scales, const uint8_t* bt,
                const uint8_t* bt_scales, float* c);
+  // GEMM on classic path `path` (BGC_CLASSIC_*): A/B in the path's element type, C double (row-major).
+  void gemm_dtype(int device, int path, int m, int n, int k, const void* a, const void* b, double* c);
   // Address-pattern walk of `fraction` of the free VRAM (see bgc_diag_hbm_walk).
   json::Value hbm_walk(int device, double fraction, uint64_t chunk_bytes, int budget_ms, uint32_t seed);
   // PCI bus id of a HIP device, lower-case ("0000:05:00.0").
@@ -160,12 +171,14 @@ class Diag {
   BGC_DIAG_ENTRY(pcie_, bgc_diag_pcie);
   BGC_DIAG_ENTRY(mfma_, bgc_diag_mfma);
   BGC_DIAG_ENTRY(lowp_, bgc_diag_mfma_lowp);
+  BGC_DIAG_ENTRY(classic_, bgc_diag_mfma_classic);
   BGC_DIAG_ENTRY(lds_, bgc_diag_lds);
   BGC_DIAG_ENTRY(burn_, bgc_diag_burn_dtype);
   BGC_DIAG_ENTRY(soak_, bgc_diag_gemm_soak);
   BGC_DIAG_ENTRY(gemm_, bgc_diag_gemm);
   BGC_DIAG_ENTRY(tiled_, bgc_diag_gemm_tiled);
   BGC_DIAG_ENTRY(mx_gemm_, bgc_diag_mx_gemm);
+  BGC_DIAG_ENTRY(gemm_dtype_, bgc_diag_gemm_dtype);
 #undef BGC_DIAG_ENTRY
 };
 

@@ -93,6 +93,10 @@ class FileLock {
   int fd_ = -1;
 };
 
+// Iterations of each classic path's rate launch: 1.9-2.1 ms fp16, 2.0-2.3 ms int8, 3.5-3.8 ms fp32 and
+// 7.0-7.1 ms fp64 on the MI355X (profiles/mfma_classic/rates.json)
+constexpr int kClassicIters = 8192;
+
 // Sweeps of the LDS rate phase: 2.4-2.9 ms on the MI355X (profiles/lds_diag/lds_rate.json)
 constexpr int kLdsRateIters = 8192;
 
@@ -124,6 +128,10 @@ class HipDiagEngine : public DiagEngine {
     if (plan.lowp) {
       r["lowp"] = d.mfma_lowp(dev, 32, 4096, seed);  // ~5 ms
       lap("lowp");
+    }
+    if (plan.classic) {
+      r["classic"] = d.mfma_classic(dev, 32, kClassicIters, seed);
+      lap("classic");
     }
     if (plan.lds) {
       r["lds"] = d.lds(dev, 4, kLdsRateIters, seed);
@@ -297,6 +305,11 @@ class ScriptedDiagEngine : public DiagEngine {
       r["lowp"] = Value::object({{"device", dev}, {"fp8_tflops", 4000.0}, {"fp4_tflops", 7000.0}, {"mismatches", 0},
                                  {"bad_cus", 0}, {"throughput_ok", true}, {"passed", true}});
     }
+    if (plan.classic) {
+      r["classic"] = Value::object({{"device", dev}, {"fp16_tflops", 2000.0}, {"int8_tops", 4000.0}, {"fp32_tflops", 150.0},
+                                    {"fp64_tflops", 75.0}, {"mismatches", 0}, {"bad_cus", 0}, {"throughput_ok", true},
+                                    {"passed", true}});
+    }
     if (plan.lds) {
       r["lds"] = Value::object({{"device", dev}, {"cus", 256}, {"cus_seen", 256}, {"bad_cus", 0}, {"mismatches", 0},
                                 {"read_tbps", 100.0}, {"rate_ok", true}, {"cu_balance", 0.97}, {"passed", true}});
@@ -353,6 +366,7 @@ Value to_json(const DiagPlan& p) {
                         {"soak_size", p.soak_size},
                         {"soak_launches", p.soak_launches},
                         {"lowp", p.lowp},
+                        {"classic", p.classic},
                         {"lds", p.lds},
                         {"burn_ms", p.burn_ms},
                         {"burn_dtype", burn_dtype_name(p.burn_dtype)}});
@@ -370,6 +384,7 @@ DiagPlan diag_plan_from_json(const Value& v) {
   p.soak_size = i32("soak_size", p.soak_size);
   p.soak_launches = i32("soak_launches", p.soak_launches);
   p.lowp = v.get("lowp").is_bool() ? v.get("lowp").as_bool() : p.lowp;
+  p.classic = v.get("classic").is_bool() ? v.get("classic").as_bool() : p.classic;
   p.lds = v.get("lds").is_bool() ? v.get("lds").as_bool() : p.lds;
   p.burn_ms = i32("burn_ms", p.burn_ms);
   if (v.get("burn_dtype").is_string()) p.burn_dtype = burn_dtype_code(v.get_string("burn_dtype"));

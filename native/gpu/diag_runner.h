@@ -41,6 +41,7 @@ struct DiagPlan {
   int soak_size = 8192;
   int soak_launches = 20;                // 0 = off
   bool lowp = true;                      // MX fp8 / fp4 matrix-core tiles and rates
+  bool classic = true;                   // fp16 / int8 / fp32 / fp64 matrix-core tiles and rates
   bool lds = true;                       // per-CU LDS march and LDS read rate
   int burn_ms = 0;                       // node-level burn phase (0 = off)
   int burn_dtype = BGC_BURN_BF16;         // its matrix-core path (bf16, MX fp8, MX fp4)
@@ -52,7 +53,7 @@ class DiagEngine {
   virtual std::string name() const = 0;
   // How far ahead node_burn schedules a common start (time a burn needs to get ready).
   virtual int start_lead_ms() const { return 0; }
-  // Everything but the burn for one GPU: {"hbm","hbm_walk","mfma","lowp","lds","gemm","pcie","soak"}.
+  // Everything but the burn for one GPU: {"hbm","hbm_walk","mfma","lowp","classic","lds","gemm","pcie","soak"}.
   // Throws on a HIP/library error.
   virtual json::Value checks(Backend& backend, const GpuInfo& g, int hip_device, const DiagPlan& plan,
                              uint32_t seed) = 0;

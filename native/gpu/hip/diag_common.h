@@ -16,6 +16,12 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef int8_t i8x16 __attribute__((ext_vector_type(16)));
+typedef float f32x1 __attribute__((ext_vector_type(1)));
+typedef double f64x1 __attribute__((ext_vector_type(1)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBlock = 256;
 
@@ -118,15 +124,15 @@ int modify_device_value(T* p, F&& f) {
   return 0;
 }
 
-// A GEMM on caller operands: upload `in`, poison C with 0xFF (NaN: an element the kernel never
+// A GEMM on caller operands: upload `in`, poison C (float or double) with 0xFF (NaN: an element the kernel never
 // writes cannot pass), launch(device operands in order, device C), download C.
 struct HostOperand {
   const void* p;
   size_t bytes;
 };
 
-template <class Launch>
-int gemm_on_host_operands(std::initializer_list<HostOperand> in, float* c, size_t c_elems, Launch&& launch) {
+template <class C, class Launch>
+int gemm_on_host_operands(std::initializer_list<HostOperand> in, C* c, size_t c_elems, Launch&& launch) {
   std::vector<DeviceBuffer> d(in.size());
   std::vector<const void*> dp;
   for (const HostOperand& h : in) {
@@ -136,11 +142,11 @@ int gemm_on_host_operands(std::initializer_list<HostOperand> in, float* c, size_
     dp.push_back(buf.p);
   }
   DeviceBuffer dc;
-  HIP_TRY(dc.alloc(c_elems * 4));
-  HIP_TRY(hipMemset(dc.p, 0xFF, c_elems * 4));
-  launch(dp.data(), dc.as<float>());
+  HIP_TRY(dc.alloc(c_elems * sizeof(C)));
+  HIP_TRY(hipMemset(dc.p, 0xFF, c_elems * sizeof(C)));
+  launch(dp.data(), dc.as<C>());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(c, dc.p, c_elems * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(c, dc.p, c_elems * sizeof(C), hipMemcpyDeviceToHost));
   return 0;
 }
 

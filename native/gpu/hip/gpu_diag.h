@@ -57,6 +57,21 @@ extern "C" {
 //    element j of 8; fp8, K 16 g .. 16 g + 15 in bytes 0..15 and K 64 + 16 g .. in bytes 16..31; fp4,
 //    K 32 g .. 32 g + 31 in 16 bytes, the even k in the low nibble; the scale byte of (rc, block g).
 //    The result lane l holds C[4 g + i][rc] in accumulator element i.
+//  * Classic matrix-core tiles (bgc_diag_mfma_classic).  h(s, tile, r, c, which) is the hash inside
+//    op() above, before trit().  A[row][k] = v(h(seed, tile, row, k, 0xA)) and B[k][col] =
+//    v(h(seed, tile, k, col, 0xB)), indexed as the bf16 tile's.  In the throughput phase v = trit for
+//    every path.  In the check phase v uses the width of the path's multipliers, and every partial
+//    sum of a dot product, in any summation order, is an integer that the accumulator holds exactly:
+//      fp16 (16x16x32):  v(h) = (h mod 1025) - 512, |v| <= 2^9 (exact in fp16: 11 significand
+//                        bits); |sum| <= 32 * 2^18 = 2^23 < 2^24, exact in the fp32 accumulator;
+//      int8 (16x16x64):  v(h) = int8(h & 0xff), |v| <= 2^7; |sum| <= 64 * 2^14 = 2^20, i32 accumulator;
+//      fp32 (16x16x4):   v(h) = (h mod 4095) - 2047; |sum| <= 4 * 2047^2 = 16760836 < 2^24;
+//      fp64 (16x16x4):   v(h) = int(h >> 6) - 2^25, |v| <= 2^25; |sum| <= 4 * 2^50 = 2^52 < 2^53.
+//    The check recomputes each dot product in integer arithmetic (64-bit for fp64), converts it once
+//    and compares for equality.  Lane l = 16 g + rc holds, of A row rc and of B column rc: fp16,
+//    k = 8 g + j in element j of 8; int8, k = 16 g + j in byte j of 16; fp32 and fp64, the single
+//    element k = g.  The result lane l holds C[4 g + i][rc] in accumulator element i, except fp64,
+//    whose lane holds C[g + 4 i][rc].
 //  * LDS march and rate (bgc_diag_lds).  A workgroup holds its CU's whole LDS as BGC_LDS_WORDS 32-bit
 //    words.  For workgroup b of a launch, s_b = mix32(seed + (b + 1) * 0x9e3779b9); word j holds
 //    P(b, j) = mix32(j ^ s_b) in pass 0 and ~P(b, j) in pass 1; the rate phase reads P.  mix32 is a
@@ -116,6 +131,32 @@ typedef struct {
 // the bf16 checks above never exercise: exact-integer fp8 and fp4 tiles with and without
 // E8M0 block scales on every CU, then the dense fp8 and fp4 rates.
 int bgc_diag_mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint32_t seed, bgc_lowp_result* out);
+// The classic matrix-core paths, in the order of every [4] below and of `path` arguments.
+#define BGC_CLASSIC_FP16 0  // v_mfma_f32_16x16x32_f16
+#define BGC_CLASSIC_INT8 1  // v_mfma_i32_16x16x64_i8
+#define BGC_CLASSIC_FP32 2  // v_mfma_f32_16x16x4_f32
+#define BGC_CLASSIC_FP64 3  // v_mfma_f64_16x16x4_f64
+typedef struct {
+  uint64_t tiles_checked;   // 16x16xK tiles verified element-wise, all four paths
+  uint64_t mismatches[4];   // output elements that differed from the exact result, by path
+  int cus_seen;             // the smallest, over the four paths, of the distinct CUs that ran that path's check
+  int bad_cus;              // CUs with >= 1 mismatch on any path
+  double rate[4];           // dense rate of each path's throughput launch: TFLOP/s, int8 in TOP/s
+  double rate_ms[4];        // device time of that launch
+  int throughput_ok;        // every throughput launch's accumulators matched exactly
+  double elapsed_ms;        // the check launches and the four timed launches
+  int bad_cu_keys[64];
+} bgc_classic_result;
+
+// The fp16, int8, fp32-input and fp64 matrix-core paths, which differ from the bf16 one by more
+// than an opcode (i32 accumulation, fp64's own multipliers and C/D map, one element per lane):
+// exact tiles with full-width operands on every CU (`waves_per_cu` 1..64), then each path's dense
+// rate over `throughput_iters` (1..65536) iterations of four MFMA chains per wave.
+int bgc_diag_mfma_classic(int device, int waves_per_cu, int throughput_iters, uint32_t seed, bgc_classic_result* out);
+// C[m,n] (double) = A[m,k] * B[k,n] on classic path `path`: A and B row-major in the path's element
+// type (IEEE half bits, int8, float, double).  m, n multiples of 16 up to 4096; k a multiple of the
+// path's K (32, 64, 4, 4) up to 8192.  Lets a test check each path's operand and result layout.
+int bgc_diag_gemm_dtype(int device, int path, int m, int n, int k, const void* a, const void* b, double* c);
 typedef struct {
   int launches;             // throughput kernels run back to back
   double elapsed_ms;        // wall time of the burn (device events)
@@ -245,6 +286,7 @@ int bgc_diag_lds(int device, int wgs_per_cu, int rate_iters, uint32_t seed, bgc_
 #define BGC_PLANT_ALL_WAVES (-1)
 #define BGC_MFMA_CHECK_ROUNDS 8  // tiles per wave of bgc_diag_mfma's check phase
 #define BGC_LOWP_CHECK_ROUNDS 2  // and of each bgc_diag_mfma_lowp variant
+#define BGC_CLASSIC_CHECK_ROUNDS 4  // and of each bgc_diag_mfma_classic path
 
 typedef struct {
   uint64_t word32_index;  // 32-bit word of the buffer
@@ -308,6 +350,12 @@ typedef struct {
 int bgc_diag_mfma_lowp_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
                                const bgc_lowp_check_plant* check, int n_check, const bgc_lowp_rate_plant* rate,
                                int n_rate, bgc_lowp_result* out);
+// The classic run takes the same plants with `variant` and `fmt` both naming the path
+// (BGC_CLASSIC_*).  `delta` is converted to the path's accumulator type; on the int8 path a delta
+// that is not a finite integer below 2^31 in magnitude is refused with "invalid arguments".
+int bgc_diag_mfma_classic_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed,
+                                  const bgc_lowp_check_plant* check, int n_check, const bgc_lowp_rate_plant* rate,
+                                  int n_rate, bgc_classic_result* out);
 
 // Delay plants: time instead of values.  Wave `wave` (global wave index, or BGC_PLANT_ALL_WAVES) of a
 // throughput launch reaches the plant point after its loop and before its comparison, where the
@@ -399,6 +447,13 @@ typedef struct {
 // `tile` of matrix-core path `path` (BGC_TILE_*), with block scales if `scaled` (MX paths only),
 // and every lane writes what it holds to lanes[0..63].
 int bgc_diag_mfma_tile(int device, int path, int scaled, uint32_t seed, uint32_t tile, bgc_tile_lane* lanes);
+typedef struct {
+  uint32_t a[4], b[4];  // the lane's A and B fragment as the MFMA takes it (fp32: 1 dword, fp64: 2, the rest 0)
+  double acc[4];        // what the matrix core returned
+  double expect[4];     // the check's own value of the same elements
+} bgc_classic_tile_lane;
+// The same for check tile `tile` of classic path `path` (BGC_CLASSIC_*).
+int bgc_diag_mfma_classic_tile(int device, int path, uint32_t seed, uint32_t tile, bgc_classic_tile_lane* lanes);
 // The march with `grid` (1..4096) workgroups; workgroup `wg` (< grid) copies its whole array, as it
 // is after pass `pass`'s (0 or 1) verify, to `data` (BGC_LDS_WORDS words).
 int bgc_diag_lds_data(int device, uint32_t seed, int wg, int pass, int grid, void* data);

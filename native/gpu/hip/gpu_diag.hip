@@ -3,7 +3,7 @@
 // kernels and their entry points, one file per family:
 //  * hbm.hip: HBM3E bandwidth (fill/copy/check), the address-in-data walk over free VRAM and
 //    the pinned host<->device copies for PCIe;
-//  * mfma.hip: the per-CU bf16 and MX fp8/fp4 matrix-core checks and throughput kernels, the
+//  * mfma.hip: the per-CU bf16, MX fp8/fp4 and fp16/int8/fp32/fp64 matrix-core checks and throughput kernels, the
 //    burn-in loop that runs them back to back, and the one-wave GEMMs on caller operands;
 //  * lds.hip: the per-CU march test of the whole Local Data Share and its read rate;
 //  * gemm_soak.hip: the ABFT-checked LDS-tiled GEMMs (gemm_soak and the 8-phase gemm_pingpong).

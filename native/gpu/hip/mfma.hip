@@ -1,11 +1,16 @@
 // Matrix cores: the per-CU bf16 MFMA check and throughput (bgc_diag_mfma), the MX fp8/fp4
-// block-scaled check and throughput (bgc_diag_mfma_lowp), the burn-in loop that runs the
-// throughput kernels back to back (bgc_diag_burn_dtype), and the one-wave-per-tile GEMMs on
-// caller operands (bgc_diag_gemm, bgc_diag_mx_gemm).
+// block-scaled check and throughput (bgc_diag_mfma_lowp), the fp16 / int8 / fp32 / fp64 checks and
+// throughputs (bgc_diag_mfma_classic), the burn-in loop that runs the throughput kernels back to
+// back (bgc_diag_burn_dtype), and the one-wave-per-tile GEMMs on caller operands (bgc_diag_gemm,
+// bgc_diag_mx_gemm, bgc_diag_gemm_dtype).
 //
-//  * A tile trait (Bf16Tile, MxTile<fmt>) says what differs between the matrix-core paths: how a
-//    lane's operands are packed, the MFMA, and the exact value of one output element.  One check
-//    kernel (mfma_check) and one throughput kernel (mfma_throughput) are instantiated over them.
+//  * A tile trait (Bf16Tile, MxTile<fmt>, ClassicTile<path, wide>) says what differs between the
+//    matrix-core paths: how a lane's operands are packed, the MFMA, its accumulator type, the row an
+//    accumulator element holds, and the exact value of one output element.  One check kernel
+//    (mfma_check) and one throughput kernel (mfma_throughput) are instantiated over them.
+//  * The classic paths (F16Path, I8Path, F32Path, F64Path) check with operands as wide as their
+//    multipliers instead of {-1,0,1}, chosen so that every partial sum stays an exact integer
+//    (gpu_diag.h); their throughput phase keeps {-1,0,1}.
 //  * The check runs one MFMA tile per wave per round with operands in {-1,0,1} (and, for MX,
 //    block scales in {1/2,1,2}) generated from a hash in registers (no memory traffic), so
 //    every product sum is an exact fp32 value and is checked element-wise against a
@@ -13,14 +18,15 @@
 //    so a faulty matrix core is attributed to (XCC, SE, SH, CU).
 //  * The throughput phase chains 4 independent accumulators per wave (dependent MFMA
 //    latency hidden by 8 waves/SIMD) and verifies acc == iters * tile exactly.
-//  * On the host, bgc_diag_mfma and bgc_diag_mfma_lowp share the per-CU bins (CuBins), the test
-//    plants (HostPlants) and the choice between a kernel's production and planted instantiation
-//    (with_plants); each fills its own result struct.
+//  * On the host, bgc_diag_mfma, bgc_diag_mfma_lowp and bgc_diag_mfma_classic share the per-CU bins
+//    (CuBins), the test plants (HostPlants) and the choice between a kernel's production and planted
+//    instantiation (with_plants); each fills its own result struct.
 //  * bgc_diag_mfma_tile runs one round of the check in one wave (mfma_tile) and returns what every
 //    lane held, for the tests of the generated tiles.
 //  * bgc_diag_mfma_delayed and bgc_diag_burn_delayed make chosen waves of a throughput launch wait on
 //    the constant clock (delay()), for the tests of the rates and times.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <utility>
 
@@ -34,24 +40,32 @@ using namespace bgc_diag;
 // c < kOperandStride (it asserts kK <= kOperandStride), so no two (r, c) of a tile share a hash.
 constexpr int kOperandStride = 128;
 
+__device__ __forceinline__ uint32_t operand_hash(uint32_t seed, uint32_t tile, int r, int c, uint32_t which) {
+  return mix32(seed ^ mix32(tile * 0x9e3779b9U + which) ^ static_cast<uint32_t>(r * kOperandStride + c));
+}
+
 __device__ __forceinline__ int operand(uint32_t seed, uint32_t tile, int r, int c, uint32_t which) {
-  uint32_t h = mix32(seed ^ mix32(tile * 0x9e3779b9U + which) ^ static_cast<uint32_t>(r * kOperandStride + c));
-  return static_cast<int>(h % 3u) - 1;
+  return static_cast<int>(operand_hash(seed, tile, r, c, which) % 3u) - 1;
 }
 
 // ---------------------------------------------------------------------------
 // Tile traits: a 16x16xkK MFMA on hash-derived operands.  Lane l holds its part of A row
 // (l & 15) and of B column (l & 15) from lane group l >> 4; the result lane l holds column
-// (l & 15), rows 4 (l >> 4) + i (the C/D map of every 16x16 MFMA).  A element (row, k) is
-// operand(seed, tile, row, k, 0xA); B element (k, col) is b_operand(seed, tile, k, col).
+// (l & 15) and, in element i of its accumulator (Acc, of Scalar), row row(l >> 4, i): 4 g + i, the
+// C/D map of every 16x16 MFMA but the fp64 one.  Lane is mfma_tile's per-lane record.  A element
+// (row, k) is operand(seed, tile, row, k, 0xA); B element (k, col) is b_operand(seed, tile, k, col).
 // mfma() takes the lane's two scale exponents, scale_exp() of its (row or column, lane group), and
-// expect() is the exact fp32 value of output element (row, col); a tile without block scales
+// expect() is the exact value of output element (row, col); a tile without block scales
 // ignores `scaled`.
 
 // v_mfma_f32_16x16x32_bf16: A is 16x32, B is 32x16, lane group g holds k = 8 g + j.
 struct Bf16Tile {
   using Frag = bf16x8;
+  using Acc = f32x4;
+  using Scalar = float;
+  using Lane = bgc_tile_lane;
   static constexpr int kK = 32;
+  static __device__ __forceinline__ int row(int g, int i) { return 4 * g + i; }
   static_assert(kK <= kOperandStride, "operand() must tell every (row, k) and (k, column) apart");
   static __device__ __forceinline__ Frag pack(uint32_t seed, uint32_t tile, int rc, int g, uint32_t which) {
     Frag v;
@@ -109,7 +123,11 @@ __device__ __forceinline__ int lowp_exp(uint32_t seed, uint32_t tile, int rc, in
 template <int kFmt>
 struct MxTile {
   using Frag = i32x8;
+  using Acc = f32x4;
+  using Scalar = float;
+  using Lane = bgc_tile_lane;
   static constexpr int kK = 128;
+  static __device__ __forceinline__ int row(int g, int i) { return 4 * g + i; }
   static_assert(kK <= kOperandStride, "operand() must tell every (row or column, k) apart");
   // 32 operands of one lane (row or column `rc`, block `g`) packed for the MFMA
   static __device__ __forceinline__ Frag pack(uint32_t seed, uint32_t tile, int rc, int g, uint32_t which) {
@@ -149,6 +167,91 @@ struct MxTile {
   }
 };
 
+// The classic matrix-core paths: fp16 (K 32), int8 (K 64), fp32 and fp64 (K 4).  A path says what
+// its MFMA takes and returns; ClassicTile below makes a tile trait of it.  Lane group g holds
+// k = kPerLane g + j in element j of its fragment, of A row rc and of B column rc (the one-hot
+// probes of tests/gpu/test_diag_classic.py read this layout and the row maps back through
+// classic_gemm).  wide() maps a hash to a check-phase operand as wide as the multipliers; the bounds
+// that keep every partial sum an exact integer are proved in gpu_diag.h.
+struct F16Path {
+  using Elem = _Float16;
+  using Frag = f16x8;
+  using Acc = f32x4;
+  using Sum = int;
+  static constexpr int kK = 32, kPerLane = 8;
+  static __device__ __forceinline__ int wide(uint32_t h) { return static_cast<int>(h % 1025u) - 512; }
+  static __device__ __forceinline__ int row(int g, int i) { return 4 * g + i; }
+  static __device__ __forceinline__ Acc mfma(Frag a, Frag b, Acc c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+};
+struct I8Path {
+  using Elem = int8_t;
+  using Frag = i8x16;
+  using Acc = i32x4;
+  using Sum = int;
+  static constexpr int kK = 64, kPerLane = 16;
+  static __device__ __forceinline__ int wide(uint32_t h) { return static_cast<int8_t>(h & 0xffu); }
+  static __device__ __forceinline__ int row(int g, int i) { return 4 * g + i; }
+  static __device__ __forceinline__ Acc mfma(Frag a, Frag b, Acc c) {
+    return __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b), c, 0, 0, 0);
+  }
+};
+struct F32Path {
+  using Elem = float;
+  using Frag = f32x1;
+  using Acc = f32x4;
+  using Sum = int;
+  static constexpr int kK = 4, kPerLane = 1;
+  static __device__ __forceinline__ int wide(uint32_t h) { return static_cast<int>(h % 4095u) - 2047; }
+  static __device__ __forceinline__ int row(int g, int i) { return 4 * g + i; }
+  static __device__ __forceinline__ Acc mfma(Frag a, Frag b, Acc c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0); }
+};
+// v_mfma_f64_16x16x4_f64 has a C/D map of its own: accumulator element i holds row g + 4 i.
+struct F64Path {
+  using Elem = double;
+  using Frag = f64x1;
+  using Acc = f64x4;
+  using Sum = long long;
+  static constexpr int kK = 4, kPerLane = 1;
+  static __device__ __forceinline__ int wide(uint32_t h) { return static_cast<int>(h >> 6) - (1 << 25); }
+  static __device__ __forceinline__ int row(int g, int i) { return g + 4 * i; }
+  static __device__ __forceinline__ Acc mfma(Frag a, Frag b, Acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a[0], b[0], c, 0, 0, 0); }
+};
+
+// The tile of a classic path: A[row][k] and B[k][col] are indexed as the bf16 tile's, with values
+// wide() of the operand hash in the check (kWide) and {-1, 0, 1} in the throughput phase.
+template <class Path, bool kWide>
+struct ClassicTile {
+  using Frag = typename Path::Frag;
+  using Acc = typename Path::Acc;
+  using Scalar = std::remove_reference_t<decltype(Acc{}[0])>;
+  using Lane = bgc_classic_tile_lane;
+  static constexpr int kK = Path::kK;
+  static_assert(kK <= kOperandStride, "operand() must tell every (row, k) and (k, column) apart");
+  static __device__ __forceinline__ int row(int g, int i) { return Path::row(g, i); }
+  static __device__ __forceinline__ int value(uint32_t seed, uint32_t tile, int r, int c, uint32_t which) {
+    return kWide ? Path::wide(operand_hash(seed, tile, r, c, which)) : operand(seed, tile, r, c, which);
+  }
+  static __device__ __forceinline__ Frag pack(uint32_t seed, uint32_t tile, int rc, int g, uint32_t which) {
+    Frag v;
+#pragma unroll
+    for (int j = 0; j < Path::kPerLane; ++j) {
+      const int k = Path::kPerLane * g + j;
+      v[j] = static_cast<typename Path::Elem>(which == 0xA ? value(seed, tile, rc, k, 0xA) : value(seed, tile, k, rc, 0xB));
+    }
+    return v;
+  }
+  static __device__ __forceinline__ Acc mfma(Frag a, Frag b, Acc acc, int /*sa*/, int /*sb*/) { return Path::mfma(a, b, acc); }
+  static __device__ __forceinline__ int scale_exp(uint32_t, uint32_t, int, int, uint32_t, bool) { return 0; }
+  // the dot product in integer VALU arithmetic, converted once
+  static __device__ __forceinline__ Scalar expect(uint32_t seed, uint32_t tile, int row, int col, bool /*scaled*/) {
+    typename Path::Sum dot = 0;
+    for (int k = 0; k < kK; ++k) {
+      dot += static_cast<typename Path::Sum>(value(seed, tile, row, k, 0xA)) * value(seed, tile, k, col, 0xB);
+    }
+    return static_cast<Scalar>(dot);
+  }
+};
+
 // Test plants (gpu_diag.h, "planted variants").  The check and throughput kernels end in a pack
 // `Plants... plants`: empty in the production instantiations, which so take no further argument and
 // call the empty plant() and delay() overloads (they compile to what they would be without), and one
@@ -164,16 +267,20 @@ using CheckPlants = PlantList<bgc_mfma_check_plant>;
 using RatePlants = PlantList<bgc_mfma_rate_plant>;
 using DelayPlants = PlantList<bgc_mfma_delay_plant>;
 
-__device__ __forceinline__ void add_at(f32x4& acc, int i, float delta) {
+// acc[i] += delta in the accumulator's type (an int8-path delta is an integer below 2^31, checked on the host)
+template <class Acc>
+__device__ __forceinline__ void add_at(Acc& acc, int i, float delta) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    if (e == i) acc[e] += delta;
+    if (e == i) acc[e] += static_cast<std::remove_reference_t<decltype(Acc{}[0])>>(delta);
   }
 }
 
 // check phase: before round `round`'s comparison
-__device__ __forceinline__ void plant(f32x4&, uint32_t /*wave*/, int /*round*/, int /*lane*/) {}
-__device__ __forceinline__ void plant(f32x4& acc, uint32_t wave, int round, int lane, CheckPlants pl) {
+template <class Acc>
+__device__ __forceinline__ void plant(Acc&, uint32_t /*wave*/, int /*round*/, int /*lane*/) {}
+template <class Acc>
+__device__ __forceinline__ void plant(Acc& acc, uint32_t wave, int round, int lane, CheckPlants pl) {
   for (int j = 0; j < pl.n; ++j) {
     const bgc_mfma_check_plant p = pl.p[j];
     if ((p.wave == BGC_PLANT_ALL_WAVES || static_cast<uint32_t>(p.wave) == wave) && p.round == round && p.lane == lane) {
@@ -183,8 +290,10 @@ __device__ __forceinline__ void plant(f32x4& acc, uint32_t wave, int round, int 
 }
 
 // throughput phase: after the loop, before the comparison
-__device__ __forceinline__ void plant(f32x4 (&)[4], uint32_t /*wave*/, int /*lane*/) {}
-__device__ __forceinline__ void plant(f32x4 (&acc)[4], uint32_t wave, int lane, RatePlants pl) {
+template <class Acc>
+__device__ __forceinline__ void plant(Acc (&)[4], uint32_t /*wave*/, int /*lane*/) {}
+template <class Acc>
+__device__ __forceinline__ void plant(Acc (&acc)[4], uint32_t wave, int lane, RatePlants pl) {
   for (int j = 0; j < pl.n; ++j) {
     const bgc_mfma_rate_plant p = pl.p[j];
     if (static_cast<uint32_t>(p.wave) != wave || p.lane != lane) continue;
@@ -194,7 +303,8 @@ __device__ __forceinline__ void plant(f32x4 (&acc)[4], uint32_t wave, int lane, 
     }
   }
 }
-__device__ __forceinline__ void plant(f32x4 (&)[4], uint32_t /*wave*/, int /*lane*/, DelayPlants) {}  // no values
+template <class Acc>
+__device__ __forceinline__ void plant(Acc (&)[4], uint32_t /*wave*/, int /*lane*/, DelayPlants) {}  // no values
 
 // throughput phase, at the same point: the wave waits for the largest `ticks` of the delay plants
 // that name it, counted on the constant clock from here.  The loop's only exit condition is the clock
@@ -226,11 +336,11 @@ __global__ __launch_bounds__(kBlock) void mfma_check(uint32_t seed, int rounds, 
     const uint32_t tile = wave * static_cast<uint32_t>(rounds) + static_cast<uint32_t>(r);
     const typename Tile::Frag a = Tile::pack(seed, tile, rc, g, 0xA);
     const typename Tile::Frag b = Tile::pack(seed, tile, rc, g, 0xB);
-    f32x4 acc = Tile::mfma(a, b, f32x4{0.f, 0.f, 0.f, 0.f}, Tile::scale_exp(seed, tile, rc, g, 0xA, scaled),
-                           Tile::scale_exp(seed, tile, rc, g, 0xB, scaled));
+    typename Tile::Acc acc = Tile::mfma(a, b, typename Tile::Acc{}, Tile::scale_exp(seed, tile, rc, g, 0xA, scaled),
+                                        Tile::scale_exp(seed, tile, rc, g, 0xB, scaled));
     plant(acc, wave, r, lane, plants...);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) bad += (acc[i] != Tile::expect(seed, tile, 4 * g + i, rc, scaled));
+    for (int i = 0; i < 4; ++i) bad += (acc[i] != Tile::expect(seed, tile, Tile::row(g, i), rc, scaled));
   }
   for (int off = 32; off > 0; off >>= 1) bad += __shfl_down(bad, off, 64);  // the wave's sum, in lane 0
   if (lane == 0) {  // one atomic per wave
@@ -242,27 +352,30 @@ __global__ __launch_bounds__(kBlock) void mfma_check(uint32_t seed, int rounds, 
 // One round of the check by one wave, for bgc_diag_mfma_tile: every lane writes out what the check
 // holds in registers (its fragments, scale exponents, accumulators and expected values).
 template <class Tile>
-__global__ __launch_bounds__(64) void mfma_tile(uint32_t seed, uint32_t tile, int scaled, bgc_tile_lane* __restrict__ lanes) {
+__global__ __launch_bounds__(64) void mfma_tile(uint32_t seed, uint32_t tile, int scaled, typename Tile::Lane* __restrict__ lanes) {
   const int lane = threadIdx.x, rc = lane & 15, g = lane >> 4;
   const typename Tile::Frag a = Tile::pack(seed, tile, rc, g, 0xA);
   const typename Tile::Frag b = Tile::pack(seed, tile, rc, g, 0xB);
-  bgc_tile_lane o = {};
-  static_assert(sizeof(a) <= sizeof(o.a), "a fragment is at most 8 dwords");
+  typename Tile::Lane o = {};
+  static_assert(sizeof(a) <= sizeof(o.a), "a fragment fits the lane record");
   __builtin_memcpy(o.a, &a, sizeof(a));
   __builtin_memcpy(o.b, &b, sizeof(b));
-  o.ea = Tile::scale_exp(seed, tile, rc, g, 0xA, scaled);
-  o.eb = Tile::scale_exp(seed, tile, rc, g, 0xB, scaled);
-  const f32x4 acc = Tile::mfma(a, b, f32x4{0.f, 0.f, 0.f, 0.f}, o.ea, o.eb);
+  const int ea = Tile::scale_exp(seed, tile, rc, g, 0xA, scaled), eb = Tile::scale_exp(seed, tile, rc, g, 0xB, scaled);
+  if constexpr (std::is_same_v<typename Tile::Lane, bgc_tile_lane>) {
+    o.ea = ea;
+    o.eb = eb;
+  }
+  const typename Tile::Acc acc = Tile::mfma(a, b, typename Tile::Acc{}, ea, eb);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     o.acc[i] = acc[i];
-    o.expect[i] = Tile::expect(seed, tile, 4 * g + i, rc, scaled);
+    o.expect[i] = Tile::expect(seed, tile, Tile::row(g, i), rc, scaled);
   }
   lanes[lane] = o;
 }
 
 // ---------------------------------------------------------------------------
-// Throughput: 4 independent accumulator chains per wave, acc == iters * tile + c.  With kTimed
+// Throughput: 4 independent accumulator chains per wave, acc == iters * tile + c in the tile's Scalar.  With kTimed
 // each wave also times itself on the 100 MHz constant clock and adds its duration to its XCC's
 // bin, so a slow (throttled / degraded) XCC shows up as an imbalance even when the whole-chip
 // rate still clears its floor.
@@ -278,9 +391,10 @@ __global__ __launch_bounds__(kBlock) void mfma_throughput(uint32_t seed, int ite
   const typename Tile::Frag a = Tile::pack(seed, tile, rc, g, 0xA);
   const typename Tile::Frag b = Tile::pack(seed, tile, rc, g, 0xB);
   // Distinct initial values keep the compiler from merging the four chains.
-  f32x4 acc[4];
+  using Scalar = typename Tile::Scalar;
+  typename Tile::Acc acc[4];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) acc[c] = f32x4{float(c), float(c), float(c), float(c)};
+  for (int c = 0; c < 4; ++c) acc[c] = typename Tile::Acc{Scalar(c), Scalar(c), Scalar(c), Scalar(c)};
   for (int it = 0; it < iters; ++it) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) acc[c] = Tile::mfma(a, b, acc[c], 0, 0);
@@ -290,9 +404,9 @@ __global__ __launch_bounds__(kBlock) void mfma_throughput(uint32_t seed, int ite
   unsigned bad = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const float e = Tile::expect(seed, tile, 4 * g + i, rc, false) * static_cast<float>(iters);
+    const Scalar e = Tile::expect(seed, tile, Tile::row(g, i), rc, false) * static_cast<Scalar>(iters);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) bad += (acc[c][i] != e + float(c));
+    for (int c = 0; c < 4; ++c) bad += (acc[c][i] != e + Scalar(c));
   }
   for (int off = 32; off > 0; off >>= 1) bad += __shfl_down(bad, off, 64);  // the wave's sum, in lane 0
   if constexpr (kTimed) {
@@ -375,6 +489,41 @@ __global__ __launch_bounds__(64) void mfma_gemm(const __bf16* __restrict__ A, co
   for (int i = 0; i < 4; ++i) C[static_cast<size_t>(tm + 4 * (lane >> 4) + i) * N + tn + rc] = acc[i];
 }
 
+// The same on a classic path: C[M,N] (double, which holds every path's results exactly) =
+// A[M,K] * B[K,N] in the path's element type, row-major.  One wave per 16x16 output tile (grid
+// N/16 x M/16), K consumed Path::kK at a time; lane l loads A row (l & 15) / B column (l & 15) at
+// k = kPerLane (l >> 4) + j straight from memory and writes rows Path::row(l >> 4, i).
+template <class Path>
+__global__ __launch_bounds__(64) void classic_gemm(const typename Path::Elem* __restrict__ A, const typename Path::Elem* __restrict__ B,
+                                                   double* __restrict__ C, int /*M*/, int N, int K) {
+  const int lane = threadIdx.x;
+  const int tm = blockIdx.y * 16, tn = blockIdx.x * 16;
+  const int rc = lane & 15, g = lane >> 4, kb = Path::kPerLane * g;
+  typename Path::Acc acc = {};
+  for (int k0 = 0; k0 < K; k0 += Path::kK) {
+    typename Path::Frag a, b;
+#pragma unroll
+    for (int j = 0; j < Path::kPerLane; ++j) {
+      a[j] = A[static_cast<size_t>(tm + rc) * K + k0 + kb + j];
+      b[j] = B[static_cast<size_t>(k0 + kb + j) * N + tn + rc];
+    }
+    acc = Path::mfma(a, b, acc);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) C[static_cast<size_t>(tm + Path::row(g, i)) * N + tn + rc] = static_cast<double>(acc[i]);
+}
+
+// `f(Path{})` for classic path 0..3 (BGC_CLASSIC_*)
+template <class F>
+void with_classic_path(int path, F&& f) {
+  switch (path) {
+    case BGC_CLASSIC_FP16: f(F16Path{}); break;
+    case BGC_CLASSIC_INT8: f(I8Path{}); break;
+    case BGC_CLASSIC_FP32: f(F32Path{}); break;
+    default: f(F64Path{}); break;
+  }
+}
+
 // `f(std::integral_constant<int, kFmt>)` for MX format 0 (fp8 e4m3) or 4 (fp4 e2m1)
 template <class F>
 void with_mx_fmt(int fmt, F&& f) {
@@ -404,7 +553,7 @@ void launch_check(int blocks, uint32_t seed, int rounds, int scaled, unsigned* c
 }
 
 template <class Tile>
-void launch_tile(uint32_t seed, uint32_t tile, int scaled, bgc_tile_lane* lanes) {
+void launch_tile(uint32_t seed, uint32_t tile, int scaled, typename Tile::Lane* lanes) {
   hipLaunchKernelGGL(mfma_tile<Tile>, dim3(1), dim3(64), 0, nullptr, seed, tile, scaled, lanes);
 }
 
@@ -499,9 +648,10 @@ struct CuBins {
   unsigned* tiles_of(int launch) const { return tiles.as<unsigned>() + static_cast<size_t>(launch) * BGC_DIAG_MAX_CU_KEYS; }
   unsigned* bad_of(int launch) const { return bad.as<unsigned>() + static_cast<size_t>(launch) * BGC_DIAG_MAX_CU_KEYS; }
   // Download and fold: the result's tiles_checked, cus_seen, bad_cus (a CU that is bad in several launches
-  // counts once) and first 64 bad_cu_keys, each launch's wrong elements, and the XCCs that ran a check.
+  // counts once) and first 64 bad_cu_keys, each launch's wrong elements, the XCCs that ran a check, and
+  // the CUs that each launch ran on (launch_cus[kLaunches]).
   template <class Result>
-  int fold(Result* out, uint64_t* const (&mismatches)[kLaunches], unsigned* xcc_mask = nullptr) const {
+  int fold(Result* out, uint64_t* const (&mismatches)[kLaunches], unsigned* xcc_mask = nullptr, int* launch_cus = nullptr) const {
     std::vector<unsigned> h_tiles(kWords), h_bad(kWords);
     HIP_TRY(hipMemcpy(h_tiles.data(), tiles.p, kWords * sizeof(unsigned), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(h_bad.data(), bad.p, kWords * sizeof(unsigned), hipMemcpyDeviceToHost));
@@ -510,6 +660,7 @@ struct CuBins {
       for (int l = 0; l < kLaunches; ++l) {
         const size_t i = static_cast<size_t>(l) * BGC_DIAG_MAX_CU_KEYS + static_cast<size_t>(k);
         seen = seen || h_tiles[i];
+        if (launch_cus && h_tiles[i]) launch_cus[l]++;
         bad_here = bad_here || h_bad[i];
         out->tiles_checked += h_tiles[i];
         *mismatches[l] += h_bad[i];
@@ -663,6 +814,84 @@ int lowp_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, 
   return 0;
 }
 
+// An int8-path plant adds its delta to an i32 accumulator: a finite integer below 2^31 in magnitude.
+bool classic_delta_ok(int path, float delta) {
+  return path != BGC_CLASSIC_INT8 || (std::isfinite(delta) && delta == std::trunc(delta) && std::fabs(delta) < 2147483648.f);
+}
+
+// one path's warm-up launch and timed throughput launch: its device time, and its failures in *fails
+template <class Path>
+int classic_rate(const Events& ev, int blocks, uint32_t seed, int iters, unsigned* fails, RatePlants plants, float* ms) {
+  using Tile = ClassicTile<Path, false>;
+  launch_rate<Tile, false>(blocks, seed, 64, fails, nullptr, nullptr, RatePlants{});
+  HIP_TRY(hipMemset(fails, 0, sizeof(unsigned)));
+  return timed(ev, ms, [&] { launch_rate<Tile, false>(blocks, seed, iters, fails, nullptr, nullptr, plants); });
+}
+
+int classic_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_lowp_check_plant* check, int n_check,
+                const bgc_lowp_rate_plant* rate, int n_rate, bgc_classic_result* out) {
+  const int rounds = BGC_CLASSIC_CHECK_ROUNDS;
+  // launches: one check and one rate launch per path (BGC_CLASSIC_*)
+  HostPlants<bgc_mfma_check_plant> check_plants;
+  HostPlants<bgc_mfma_rate_plant> rate_plants;
+  bool ok = out && waves_per_cu > 0 && waves_per_cu <= 64 && throughput_iters > 0 && throughput_iters <= (1 << 16) &&
+            check_plants.take(check, n_check, 4, [&](const auto& at) { return check_plant_ok(at, rounds); }) &&
+            rate_plants.take(rate, n_rate, 4, rate_plant_ok);
+  for (int j = 0; ok && j < n_check; ++j) ok = classic_delta_ok(check[j].variant, check[j].at.delta);
+  for (int j = 0; ok && j < n_rate; ++j) ok = classic_delta_ok(rate[j].fmt, rate[j].at.delta);
+  if (!ok) {
+    g_last_error = "invalid arguments";
+    return 1;
+  }
+  std::memset(out, 0, sizeof(*out));
+  HIP_TRY(hipSetDevice(device));
+  const int blocks = wave_blocks(device, waves_per_cu);
+  if (check_plants.upload(blocks) != 0 || rate_plants.upload(blocks) != 0) return 1;
+  CuBins<4> bins;  // by path
+  if (bins.alloc() != 0) return 1;
+  DeviceBuffer fails;
+  HIP_TRY(fails.alloc(4 * sizeof(unsigned), true));
+  auto* f = fails.as<unsigned>();
+  Events ev;
+  HIP_TRY(ev.create());
+  float total = 0.f;
+  if (timed(ev, &total, [&] {
+        for (int p = 0; p < 4; ++p) {
+          with_classic_path(p, [&](auto path) {
+            launch_check<ClassicTile<decltype(path), true>>(blocks, seed, rounds, 0, bins.tiles_of(p), bins.bad_of(p), check_plants.of(p));
+          });
+        }
+      }) != 0) {
+    return 1;
+  }
+  // per path: a warm-up launch, then one timed launch
+  for (int p = 0; p < 4; ++p) {
+    int rc = 0;
+    float ms = 0.f;
+    double flops = 0;
+    with_classic_path(p, [&](auto path) {
+      rc = classic_rate<decltype(path)>(ev, blocks, seed, throughput_iters, f + p, rate_plants.of(p), &ms);
+      flops = rate_flops<ClassicTile<decltype(path), false>>(blocks, throughput_iters);
+    });
+    if (rc != 0) return 1;
+    out->rate_ms[p] = ms;
+    out->rate[p] = ms > 0 ? flops / (ms * 1e-3) / 1e12 : 0.0;
+    total += ms;
+  }
+  unsigned h_f[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpy(h_f, f, sizeof(h_f), hipMemcpyDeviceToHost));
+  int path_cus[4] = {0, 0, 0, 0};
+  if (bins.fold(out, {&out->mismatches[0], &out->mismatches[1], &out->mismatches[2], &out->mismatches[3]}, nullptr, path_cus) != 0) {
+    return 1;
+  }
+  // Consecutive launches need not land on the same CUs, so the union over the paths says nothing about
+  // one path: report the coverage that every path reached.
+  out->cus_seen = *std::min_element(path_cus, path_cus + 4);
+  out->throughput_ok = h_f[0] == 0 && h_f[1] == 0 && h_f[2] == 0 && h_f[3] == 0;
+  out->elapsed_ms = total;
+  return 0;
+}
+
 // bgc_diag_burn_dtype, and bgc_diag_burn_delayed with every wave of the launches from `first_delayed_launch`
 // on delayed by `ticks` (0: no launch is delayed, the production burn)
 int burn_run(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype, int first_delayed_launch, uint32_t ticks,
@@ -756,6 +985,49 @@ int bgc_diag_mfma_lowp(int device, int waves_per_cu, int throughput_iters, uint3
 int bgc_diag_mfma_lowp_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_lowp_check_plant* check,
                                int n_check, const bgc_lowp_rate_plant* rate, int n_rate, bgc_lowp_result* out) {
   return lowp_run(device, waves_per_cu, throughput_iters, seed, check, n_check, rate, n_rate, out);
+}
+
+int bgc_diag_mfma_classic(int device, int waves_per_cu, int throughput_iters, uint32_t seed, bgc_classic_result* out) {
+  return classic_run(device, waves_per_cu, throughput_iters, seed, nullptr, 0, nullptr, 0, out);
+}
+
+int bgc_diag_mfma_classic_planted(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_lowp_check_plant* check,
+                                  int n_check, const bgc_lowp_rate_plant* rate, int n_rate, bgc_classic_result* out) {
+  return classic_run(device, waves_per_cu, throughput_iters, seed, check, n_check, rate, n_rate, out);
+}
+
+int bgc_diag_mfma_classic_tile(int device, int path, uint32_t seed, uint32_t tile, bgc_classic_tile_lane* lanes) {
+  if (!lanes || path < BGC_CLASSIC_FP16 || path > BGC_CLASSIC_FP64) {
+    g_last_error = "invalid arguments";
+    return 1;
+  }
+  HIP_TRY(hipSetDevice(device));
+  DeviceBuffer d;
+  HIP_TRY(d.alloc(64 * sizeof(bgc_classic_tile_lane), true));
+  with_classic_path(path, [&](auto p) { launch_tile<ClassicTile<decltype(p), true>>(seed, tile, 0, d.as<bgc_classic_tile_lane>()); });
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(lanes, d.p, 64 * sizeof(bgc_classic_tile_lane), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int bgc_diag_gemm_dtype(int device, int path, int m, int n, int k, const void* a, const void* b, double* c) {
+  static const int kPathK[4] = {F16Path::kK, I8Path::kK, F32Path::kK, F64Path::kK};
+  static const size_t kElemBytes[4] = {sizeof(F16Path::Elem), sizeof(I8Path::Elem), sizeof(F32Path::Elem), sizeof(F64Path::Elem)};
+  if (!a || !b || !c || path < BGC_CLASSIC_FP16 || path > BGC_CLASSIC_FP64 || m <= 0 || n <= 0 || k <= 0 || m % 16 || n % 16 ||
+      k % kPathK[path] || m > 4096 || n > 4096 || k > 8192) {
+    g_last_error = "invalid arguments (path 0..3; M, N multiples of 16 up to 4096; K a multiple of the path's K up to 8192)";
+    return 1;
+  }
+  HIP_TRY(hipSetDevice(device));
+  const size_t a_bytes = static_cast<size_t>(m) * k * kElemBytes[path], b_bytes = static_cast<size_t>(k) * n * kElemBytes[path];
+  return gemm_on_host_operands({{a, a_bytes}, {b, b_bytes}}, c, static_cast<size_t>(m) * n, [&](const void* const* d, double* dc) {
+    with_classic_path(path, [&](auto p) {
+      using Path = decltype(p);
+      using Elem = typename Path::Elem;
+      hipLaunchKernelGGL(classic_gemm<Path>, dim3(n / 16, m / 16), dim3(64), 0, nullptr, static_cast<const Elem*>(d[0]),
+                         static_cast<const Elem*>(d[1]), dc, m, n, k);
+    });
+  });
 }
 
 int bgc_diag_mfma_tile(int device, int path, int scaled, uint32_t seed, uint32_t tile, bgc_tile_lane* lanes) {

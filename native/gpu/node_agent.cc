@@ -57,6 +57,7 @@ NodeAgentConfig NodeAgentConfig::from_env(const EnvConfig& env) {
   c.diag_soak_size = static_cast<int>(env.u64_or("diag_soak_size", static_cast<uint64_t>(c.diag_soak_size)));
   c.diag_soak_launches = static_cast<int>(env.u64_or("diag_soak_launches", static_cast<uint64_t>(c.diag_soak_launches)));
   c.diag_lowp = env.boolean_or("diag_lowp", c.diag_lowp);
+  c.diag_classic = env.boolean_or("diag_classic", c.diag_classic);
   c.diag_lds = env.boolean_or("diag_lds", c.diag_lds);
   c.pod_resources_socket = env.str_or("pod_resources_socket", c.pod_resources_socket);
   HealthPolicy& h = c.health;
@@ -458,6 +459,7 @@ DiagPlan NodeAgent::diag_plan() const {
   p.soak_size = cfg_.diag_soak_size;
   p.soak_launches = cfg_.diag_soak_launches;
   p.lowp = cfg_.diag_lowp;
+  p.classic = cfg_.diag_classic;
   p.lds = cfg_.diag_lds;
   p.burn_ms = static_cast<int>(cfg_.diag_burn_ms);
   return p;
@@ -552,6 +554,11 @@ void NodeAgent::record_diag_gauges(size_t i, const Value& r) {
       {"amd_gpu_diag_xcc_balance", "Diagnostics: fastest/slowest XCC wave time", "mfma", "xcc_balance"},
       {"amd_gpu_diag_fp8_tflops", "Diagnostics: MX fp8 MFMA TFLOP/s (register operands)", "lowp", "fp8_tflops"},
       {"amd_gpu_diag_fp4_tflops", "Diagnostics: MX fp4 MFMA TFLOP/s (register operands)", "lowp", "fp4_tflops"},
+      {"amd_gpu_diag_fp16_tflops", "Diagnostics: fp16 MFMA TFLOP/s (register operands)", "classic", "fp16_tflops"},
+      {"amd_gpu_diag_int8_tops", "Diagnostics: int8 MFMA TOP/s (register operands)", "classic", "int8_tops"},
+      {"amd_gpu_diag_fp32_tflops", "Diagnostics: fp32-input MFMA TFLOP/s (register operands)", "classic", "fp32_tflops"},
+      {"amd_gpu_diag_fp64_tflops", "Diagnostics: fp64 MFMA TFLOP/s (register operands)", "classic", "fp64_tflops"},
+      {"amd_gpu_diag_classic_bad_cus", "Diagnostics: CUs with a wrong fp16 / int8 / fp32 / fp64 MFMA tile element", "classic", "bad_cus"},
       {"amd_gpu_diag_lds_read_tbps", "Diagnostics: LDS read TB/s, all CUs", "lds", "read_tbps"},
       {"amd_gpu_diag_lds_bad_cus", "Diagnostics: CUs whose LDS march read back a wrong word", "lds", "bad_cus"},
       {"amd_gpu_diag_soak_tflops", "Diagnostics: LDS-tiled MFMA GEMM soak TFLOP/s", "soak", "tflops_mean"},
@@ -570,7 +577,9 @@ void NodeAgent::record_diag_gauges(size_t i, const Value& r) {
                            << " ms, read " << get("hbm", "read_gbps") << " GB/s, walk "
                            << get("hbm_walk", "bytes_covered") / 1e9 << " GB, mfma " << get("mfma", "tflops")
                            << " TFLOP/s, xcc balance " << get("mfma", "xcc_balance") << ", mx fp8/fp4 "
-                           << get("lowp", "fp8_tflops") << "/" << get("lowp", "fp4_tflops") << " TFLOP/s, lds "
+                           << get("lowp", "fp8_tflops") << "/" << get("lowp", "fp4_tflops") << " TFLOP/s, fp16/int8/fp32/fp64 "
+                           << get("classic", "fp16_tflops") << "/" << get("classic", "int8_tops") << "/"
+                           << get("classic", "fp32_tflops") << "/" << get("classic", "fp64_tflops") << " TFLOP/s, lds "
                            << get("lds", "read_tbps") << " TB/s, soak "
                            << get("soak", "tflops_mean") << " TFLOP/s, pcie " << get("pcie", "h2d_gbps") << "/"
                            << get("pcie", "d2h_gbps") << " GB/s, burn " << get("burn", "tflops_mean") << " TFLOP/s";

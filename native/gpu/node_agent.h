@@ -101,6 +101,8 @@ struct NodeAgentConfig {
   int diag_soak_launches = 20;
   // MX block-scaled fp8 / fp4 matrix-core tiles (with and without E8M0 scales) and rates
   bool diag_lowp = true;
+  // fp16 / int8 / fp32 / fp64 matrix-core tiles with full-width operands, and their rates
+  bool diag_classic = true;
   // March test of every CU's whole Local Data Share, and the LDS read rate
   bool diag_lds = true;
   DiagFloors diag_floors = DiagFloors::mi355x_defaults();

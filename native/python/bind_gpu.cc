@@ -232,6 +232,9 @@ void register_gpu(py::module_& m) {
   m.def("diag_mfma_lowp", [](int device, int waves_per_cu, int iters, unsigned seed) {
     return dump_nogil([&] { return Diag::instance().mfma_lowp(device, waves_per_cu, iters, seed); });
   }, py::arg("device"), py::arg("waves_per_cu") = 32, py::arg("iters") = 4096, py::arg("seed") = 0x5eed);
+  m.def("diag_mfma_classic", [](int device, int waves_per_cu, int iters, unsigned seed) {
+    return dump_nogil([&] { return Diag::instance().mfma_classic(device, waves_per_cu, iters, seed); });
+  }, py::arg("device"), py::arg("waves_per_cu") = 32, py::arg("iters") = 8192, py::arg("seed") = 0x5eed);
   m.def("diag_lds", [](int device, int wgs_per_cu, int rate_iters, unsigned seed) {
     return dump_nogil([&] { return Diag::instance().lds(device, wgs_per_cu, rate_iters, seed); });
   }, py::arg("device"), py::arg("wgs_per_cu") = 4, py::arg("rate_iters") = 8192, py::arg("seed") = 0x5eed);
@@ -260,6 +263,21 @@ void register_gpu(py::module_& m) {
     });
   }, py::arg("device"), py::arg("fmt"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("a"), py::arg("a_scales"),
      py::arg("bt"), py::arg("bt_scales"));
+  // A and B as bytes in classic path `path`'s element type (2, 1, 4, 8 bytes); C as bytes of doubles
+  m.def("diag_gemm_dtype", [](int device, int path, int mm, int nn, int kk, const std::string& a, const std::string& b) {
+    static const size_t kElemBytes[4] = {2, 1, 4, 8};
+    // a shape the library may accept gets its operand sizes checked and a C; any other is refused there
+    const bool sized = path >= 0 && path < 4 && mm > 0 && nn > 0 && kk > 0 && mm <= 4096 && nn <= 4096 && kk <= 8192;
+    if (sized && (a.size() != static_cast<size_t>(mm) * kk * kElemBytes[path] || b.size() != static_cast<size_t>(kk) * nn * kElemBytes[path])) {
+      throw std::invalid_argument("A must be M*K and B K*N elements of the path's type");
+    }
+    std::string c(sized ? static_cast<size_t>(mm) * nn * sizeof(double) : 0, '\0');
+    {
+      py::gil_scoped_release nogil;
+      Diag::instance().gemm_dtype(device, path, mm, nn, kk, a.data(), b.data(), reinterpret_cast<double*>(c.data()));
+    }
+    return py::bytes(c);
+  }, py::arg("device"), py::arg("path"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("a"), py::arg("b"));
   m.def("diag_hbm_walk", [](int device, double fraction, unsigned long long chunk_bytes, int budget_ms, unsigned seed) {
     return dump_nogil([&] { return Diag::instance().hbm_walk(device, fraction, chunk_bytes, budget_ms, seed); });
   }, py::arg("device"), py::arg("fraction") = 0.9, py::arg("chunk_bytes") = 4ULL << 30, py::arg("budget_ms") = 20000,
@@ -325,6 +343,16 @@ void register_gpu(py::module_& m) {
     for (const auto& [variant, wave, round, lane, i, delta] : check) c.push_back({variant, {wave, round, lane, i, delta}});
     for (const auto& [fmt, wave, lane, chain, i, delta] : rate) r.push_back({fmt, {wave, lane, chain, i, delta}});
     return planted("low-precision mfma diag", BGC_DIAG_ENTRY(bgc_diag_mfma_lowp_planted), device, waves_per_cu, iters, seed,
+                   c.data(), count(c), r.data(), count(r));
+  }, py::arg("device"), py::arg("waves_per_cu"), py::arg("iters"), py::arg("seed"), py::arg("check_plants"),
+     py::arg("rate_plants"));
+  m.def("diag_mfma_classic_planted", [](int device, int waves_per_cu, int iters, unsigned seed, const std::vector<LowpPlant>& check,
+                                        const std::vector<LowpPlant>& rate) {
+    std::vector<bgc_lowp_check_plant> c;
+    std::vector<bgc_lowp_rate_plant> r;
+    for (const auto& [path, wave, round, lane, i, delta] : check) c.push_back({path, {wave, round, lane, i, delta}});
+    for (const auto& [path, wave, lane, chain, i, delta] : rate) r.push_back({path, {wave, lane, chain, i, delta}});
+    return planted("classic mfma diag", BGC_DIAG_ENTRY(bgc_diag_mfma_classic_planted), device, waves_per_cu, iters, seed,
                    c.data(), count(c), r.data(), count(r));
   }, py::arg("device"), py::arg("waves_per_cu"), py::arg("iters"), py::arg("seed"), py::arg("check_plants"),
      py::arg("rate_plants"));
@@ -406,6 +434,16 @@ void register_gpu(py::module_& m) {
     }
     return py::bytes(lanes);
   }, py::arg("device"), py::arg("path"), py::arg("scaled"), py::arg("seed"), py::arg("tile"));
+  // the 64 bgc_classic_tile_lane of one classic-path tile, as bytes
+  m.def("diag_mfma_classic_tile", [](int device, int path, unsigned seed, unsigned tile) {
+    std::string lanes(64 * sizeof(bgc_classic_tile_lane), '\0');
+    {
+      py::gil_scoped_release nogil;
+      Diag::instance().check("classic mfma tile", BGC_DIAG_ENTRY(bgc_diag_mfma_classic_tile)(
+                                                      device, path, seed, tile, reinterpret_cast<bgc_classic_tile_lane*>(lanes.data())));
+    }
+    return py::bytes(lanes);
+  }, py::arg("device"), py::arg("path"), py::arg("seed"), py::arg("tile"));
   // the BGC_LDS_WORDS words of one march workgroup, as bytes
   m.def("diag_lds_data", [](int device, unsigned seed, int wg, int pass, int grid) {
     std::string data(4 * BGC_LDS_WORDS, '\0');
