@@ -277,7 +277,7 @@ def _bf16_bytes(x):
 
 
 def gemm(a, b, device=0):
-    """C = A @ B on the one-wave-per-tile MFMA kernel (mfma_gemm).  A is MxK, B is KxN; M and N
+    """C = A @ B on the one-wave-per-tile MFMA kernel (dense_gemm).  A is MxK, B is KxN; M and N
     must be multiples of 16 (up to 4096) and K of 32 (up to 8192).  Returns an fp32 numpy array
     MxN."""
     m, k = a.shape
@@ -290,7 +290,7 @@ def gemm(a, b, device=0):
 
 def gemm_dtype(a, b, path, device=0):
     """C = A @ B on classic path `path` ("fp16", "int8", "fp32", "fp64"), one wave per 16x16 tile
-    (classic_gemm).  A is MxK, B is KxN, converted to the path's element type; M and N must be
+    (dense_gemm).  A is MxK, B is KxN, converted to the path's element type; M and N must be
     multiples of 16 (up to 4096) and K of the path's K (up to 8192).  Returns a float64 numpy array
     MxN, which holds every path's results exactly."""
     m, k = a.shape

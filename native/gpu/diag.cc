@@ -92,6 +92,14 @@ std::string Diag::device_arch(int device) {
   return buf;
 }
 
+// the bad CU keys that a result holds (its first 64), as an array
+template <class Result>
+json::Value bad_cu_keys(const Result& r) {
+  json::Value keys = json::Value::array();
+  for (int i = 0; i < r.bad_cus && i < 64; ++i) keys.push_back(r.bad_cu_keys[i]);
+  return keys;
+}
+
 json::Value to_json(int device, const bgc_hbm_result& r) {
   json::Value v = json::Value::object();
   v["device"] = device;
@@ -115,9 +123,7 @@ json::Value to_json(int device, const bgc_mfma_result& r) {
   v["cus_seen"] = r.cus_seen;
   v["xccs_seen"] = r.xccs_seen;
   v["bad_cus"] = r.bad_cus;
-  json::Value bad = json::Value::array();
-  for (int i = 0; i < r.bad_cus && i < 64; ++i) bad.push_back(r.bad_cu_keys[i]);
-  v["bad_cu_keys"] = bad;
+  v["bad_cu_keys"] = bad_cu_keys(r);
   v["tflops"] = r.tflops;
   v["throughput_ok"] = r.throughput_ok != 0;
   json::Value xw = json::Value::array(), xus = json::Value::array();
@@ -134,8 +140,6 @@ json::Value to_json(int device, const bgc_mfma_result& r) {
 }
 
 json::Value to_json(int device, const bgc_lowp_result& r) {
-  json::Value bad = json::Value::array();
-  for (int i = 0; i < r.bad_cus && i < 64; ++i) bad.push_back(r.bad_cu_keys[i]);
   const uint64_t mism = r.fp8_mismatches + r.fp8_scaled_mismatches + r.fp4_mismatches + r.fp4_scaled_mismatches;
   return json::Value::object({{"device", device},
                               {"tiles_checked", static_cast<unsigned long long>(r.tiles_checked)},
@@ -146,7 +150,7 @@ json::Value to_json(int device, const bgc_lowp_result& r) {
                               {"mismatches", static_cast<unsigned long long>(mism)},
                               {"cus_seen", r.cus_seen},
                               {"bad_cus", r.bad_cus},
-                              {"bad_cu_keys", bad},
+                              {"bad_cu_keys", bad_cu_keys(r)},
                               {"fp8_tflops", r.fp8_tflops},
                               {"fp4_tflops", r.fp4_tflops},
                               {"throughput_ok", r.throughput_ok != 0},
@@ -155,8 +159,6 @@ json::Value to_json(int device, const bgc_lowp_result& r) {
 }
 
 json::Value to_json(int device, const bgc_classic_result& r) {
-  json::Value bad = json::Value::array();
-  for (int i = 0; i < r.bad_cus && i < 64; ++i) bad.push_back(r.bad_cu_keys[i]);
   json::Value ms = json::Value::array();
   for (int p = 0; p < 4; ++p) ms.push_back(r.rate_ms[p]);
   const uint64_t mism = r.mismatches[0] + r.mismatches[1] + r.mismatches[2] + r.mismatches[3];
@@ -169,7 +171,7 @@ json::Value to_json(int device, const bgc_classic_result& r) {
                               {"mismatches", static_cast<unsigned long long>(mism)},
                               {"cus_seen", r.cus_seen},
                               {"bad_cus", r.bad_cus},
-                              {"bad_cu_keys", bad},
+                              {"bad_cu_keys", bad_cu_keys(r)},
                               {"fp16_tflops", r.rate[BGC_CLASSIC_FP16]},
                               {"int8_tops", r.rate[BGC_CLASSIC_INT8]},
                               {"fp32_tflops", r.rate[BGC_CLASSIC_FP32]},
@@ -181,8 +183,6 @@ json::Value to_json(int device, const bgc_classic_result& r) {
 }
 
 json::Value to_json(int device, const bgc_lds_result& r) {
-  json::Value bad = json::Value::array();
-  for (int i = 0; i < r.bad_cus && i < 64; ++i) bad.push_back(r.bad_cu_keys[i]);
   char bits[16];
   std::snprintf(bits, sizeof(bits), "0x%08x", r.bad_bits);
   const bool clean = r.mismatches == 0;
@@ -190,7 +190,7 @@ json::Value to_json(int device, const bgc_lds_result& r) {
                               {"cus", r.cus},
                               {"cus_seen", r.cus_seen},
                               {"bad_cus", r.bad_cus},
-                              {"bad_cu_keys", bad},
+                              {"bad_cu_keys", bad_cu_keys(r)},
                               {"words_checked", static_cast<unsigned long long>(r.words_checked)},
                               {"mismatches", static_cast<unsigned long long>(r.mismatches)},
                               {"first_bad_cu_key", clean ? json::Value() : json::Value(r.first_bad_cu_key)},

@@ -108,6 +108,13 @@ int timed(const Events& ev, float* ms, Launch&& launch, hipStream_t s = nullptr)
   return 0;
 }
 
+// One more bad CU of a result: counted, and its key kept while bad_cu_keys has room.
+template <class Result>
+void note_bad_cu(Result* out, int key) {
+  if (out->bad_cus < 64) out->bad_cu_keys[out->bad_cus] = key;
+  out->bad_cus++;
+}
+
 // Test plants (gpu_diag.h, "planted variants").  A plant list is `n` entries at `plants`.
 inline bool plant_list_ok(const void* plants, int n) {
   return n >= 0 && n <= BGC_DIAG_MAX_PLANTS && (n == 0 || plants);

@@ -42,36 +42,37 @@ extern "C" {
 //    trit(mix32(u32(i) ^ mix32(u32(i >> 32) + s))) as bf16; A[m][k] uses s = seed, Bt[n][k] (B
 //    transposed) s = seed ^ 0xB7B7B7B7.  The reference checksums are rref = A (B 1), the row sums
 //    of C, and cref = (1^T A) B, its column sums.
-//  * Matrix-core tiles (bgc_diag_mfma, bgc_diag_mfma_lowp, bgc_diag_burn_dtype).
-//    op(s, tile, r, c, which) = trit(mix32(s ^ mix32(tile * 0x9e3779b9 + which) ^ u32(128 r + c))).
-//    bf16 tile (16x16x32): A[row][k] = op(seed, tile, row, k, 0xA), B[k][col] = op(seed, tile, k, col, 0xB),
-//    as bf16 values.  MX tile (16x16x128): A[row][k] = op(seed, tile, row, c(k), 0xA), B[k][col] =
+//  * Matrix-core tiles (bgc_diag_mfma, bgc_diag_mfma_lowp, bgc_diag_mfma_classic, bgc_diag_burn_dtype).
+//    h(s, tile, r, c, which) = mix32(s ^ mix32(tile * 0x9e3779b9 + which) ^ u32(128 r + c)) and
+//    op(s, tile, r, c, which) = trit(h(s, tile, r, c, which)).  A check wave w takes tiles
+//    w * rounds .. w * rounds + rounds - 1, a throughput wave w tile w.
+//  * Dense tiles: bf16 (16x16x32) and the classic fp16 (16x16x32), int8 (16x16x64), fp32 and fp64
+//    (16x16x4).  A[row][k] = v(h(seed, tile, row, k, 0xA)) and B[k][col] = v(h(seed, tile, k, col, 0xB)) in
+//    the path's element type.  v = trit, so the elements are op(), in the bf16 check and in every
+//    path's throughput phase.  In a classic path's check phase v uses the width of the path's
+//    multipliers, and every partial sum of a dot product, in any summation order, is an integer that
+//    the accumulator holds exactly:
+//      fp16:  v(h) = (h mod 1025) - 512, |v| <= 2^9 (exact in fp16: 11 significand bits);
+//             |sum| <= 32 * 2^18 = 2^23 < 2^24, exact in the fp32 accumulator;
+//      int8:  v(h) = int8(h & 0xff), |v| <= 2^7; |sum| <= 64 * 2^14 = 2^20, i32 accumulator;
+//      fp32:  v(h) = (h mod 4095) - 2047; |sum| <= 4 * 2047^2 = 16760836 < 2^24;
+//      fp64:  v(h) = int(h >> 6) - 2^25, |v| <= 2^25; |sum| <= 4 * 2^50 = 2^52 < 2^53.
+//    The check recomputes each dot product in integer arithmetic (64-bit for fp64), converts it once
+//    and compares for equality.  Lane l = 16 g + rc holds, of A row rc and of B column rc: bf16 and
+//    fp16, k = 8 g + j in element j of 8; int8, k = 16 g + j in byte j of 16; fp32 and fp64, the single
+//    element k = g.  The result lane l holds C[4 g + i][rc] in accumulator element i, except fp64,
+//    whose lane holds C[g + 4 i][rc].
+//  * MX tiles (16x16x128): A[row][k] = op(seed, tile, row, c(k), 0xA), B[k][col] =
 //    op(seed, tile, col, c(k), 0xB), as e4m3 codes 0x38 / 0x00 / 0xB8 or e2m1 codes 0x2 / 0x0 / 0xA for
 //    1 / 0 / -1.  c(k) numbers the elements in the order the lanes hold them (below): fp4, c(k) = k;
 //    fp8, c(k) = 32 ((k mod 64) / 16) + 16 (k / 64) + k mod 16.  Scale exponents (E8M0 byte 127 + e)
 //    of the K-block blk = k / 32: ea[row][blk] = op(seed ^ 0x5ca1e, tile, row, blk, 0xA), eb[col][blk] =
 //    op(seed ^ 0x5ca1e, tile, col, blk, 0xB) in the scaled variants, 0 otherwise.  The exact result is
-//    C[row][col] = sum_blk 2^(ea[row][blk] + eb[col][blk]) sum_{k in blk} A[row][k] B[k][col].  A check
-//    wave w takes tiles w * rounds .. w * rounds + rounds - 1, a throughput wave w tile w.
-//    Lane l = 16 g + rc of the wave holds, of A row rc and of B column rc: bf16, k = 8 g + j in
-//    element j of 8; fp8, K 16 g .. 16 g + 15 in bytes 0..15 and K 64 + 16 g .. in bytes 16..31; fp4,
-//    K 32 g .. 32 g + 31 in 16 bytes, the even k in the low nibble; the scale byte of (rc, block g).
-//    The result lane l holds C[4 g + i][rc] in accumulator element i.
-//  * Classic matrix-core tiles (bgc_diag_mfma_classic).  h(s, tile, r, c, which) is the hash inside
-//    op() above, before trit().  A[row][k] = v(h(seed, tile, row, k, 0xA)) and B[k][col] =
-//    v(h(seed, tile, k, col, 0xB)), indexed as the bf16 tile's.  In the throughput phase v = trit for
-//    every path.  In the check phase v uses the width of the path's multipliers, and every partial
-//    sum of a dot product, in any summation order, is an integer that the accumulator holds exactly:
-//      fp16 (16x16x32):  v(h) = (h mod 1025) - 512, |v| <= 2^9 (exact in fp16: 11 significand
-//                        bits); |sum| <= 32 * 2^18 = 2^23 < 2^24, exact in the fp32 accumulator;
-//      int8 (16x16x64):  v(h) = int8(h & 0xff), |v| <= 2^7; |sum| <= 64 * 2^14 = 2^20, i32 accumulator;
-//      fp32 (16x16x4):   v(h) = (h mod 4095) - 2047; |sum| <= 4 * 2047^2 = 16760836 < 2^24;
-//      fp64 (16x16x4):   v(h) = int(h >> 6) - 2^25, |v| <= 2^25; |sum| <= 4 * 2^50 = 2^52 < 2^53.
-//    The check recomputes each dot product in integer arithmetic (64-bit for fp64), converts it once
-//    and compares for equality.  Lane l = 16 g + rc holds, of A row rc and of B column rc: fp16,
-//    k = 8 g + j in element j of 8; int8, k = 16 g + j in byte j of 16; fp32 and fp64, the single
-//    element k = g.  The result lane l holds C[4 g + i][rc] in accumulator element i, except fp64,
-//    whose lane holds C[g + 4 i][rc].
+//    C[row][col] = sum_blk 2^(ea[row][blk] + eb[col][blk]) sum_{k in blk} A[row][k] B[k][col].
+//    Lane l = 16 g + rc of the wave holds, of A row rc and of B column rc: fp8, K 16 g .. 16 g + 15 in
+//    bytes 0..15 and K 64 + 16 g .. in bytes 16..31; fp4, K 32 g .. 32 g + 31 in 16 bytes, the even k in
+//    the low nibble; the scale byte of (rc, block g).  The result lane l holds C[4 g + i][rc] in
+//    accumulator element i.
 //  * LDS march and rate (bgc_diag_lds).  A workgroup holds its CU's whole LDS as BGC_LDS_WORDS 32-bit
 //    words.  For workgroup b of a launch, s_b = mix32(seed + (b + 1) * 0x9e3779b9); word j holds
 //    P(b, j) = mix32(j ^ s_b) in pass 0 and ~P(b, j) in pass 1; the rate phase reads P.  mix32 is a

@@ -295,8 +295,7 @@ int lds_run(int device, int wgs_per_cu, int rate_iters, uint32_t seed, const bgc
           out->first_bad_cu_key = k;
           out->first_bad_word = m.first;
         }
-        if (out->bad_cus < 64) out->bad_cu_keys[out->bad_cus] = k;
-        out->bad_cus++;
+        note_bad_cu(out, k);
       }
     }
     const RateBin& r = h_rate[static_cast<size_t>(k)];

@@ -4,11 +4,12 @@
 // back (bgc_diag_burn_dtype), and the one-wave-per-tile GEMMs on caller operands (bgc_diag_gemm,
 // bgc_diag_mx_gemm, bgc_diag_gemm_dtype).
 //
-//  * A tile trait (Bf16Tile, MxTile<fmt>, ClassicTile<path, wide>) says what differs between the
-//    matrix-core paths: how a lane's operands are packed, the MFMA, its accumulator type, the row an
+//  * A tile trait (DenseTile<path, wide>, MxTile<fmt>) says what differs between the matrix-core
+//    paths: how a lane's operands are packed, the MFMA, its accumulator type, the row an
 //    accumulator element holds, and the exact value of one output element.  One check kernel
 //    (mfma_check) and one throughput kernel (mfma_throughput) are instantiated over them.
-//  * The classic paths (F16Path, I8Path, F32Path, F64Path) check with operands as wide as their
+//  * The dense paths (Bf16Path and the classic F16Path, I8Path, F32Path, F64Path) share one tile
+//    layout and one GEMM kernel (dense_gemm).  The classic ones check with operands as wide as their
 //    multipliers instead of {-1,0,1}, chosen so that every partial sum stays an exact integer
 //    (gpu_diag.h); their throughput phase keeps {-1,0,1}.
 //  * The check runs one MFMA tile per wave per round with operands in {-1,0,1} (and, for MX,
@@ -18,9 +19,11 @@
 //    so a faulty matrix core is attributed to (XCC, SE, SH, CU).
 //  * The throughput phase chains 4 independent accumulators per wave (dependent MFMA
 //    latency hidden by 8 waves/SIMD) and verifies acc == iters * tile exactly.
-//  * On the host, bgc_diag_mfma, bgc_diag_mfma_lowp and bgc_diag_mfma_classic share the per-CU bins
-//    (CuBins), the test plants (HostPlants) and the choice between a kernel's production and planted
-//    instantiation (with_plants); each fills its own result struct.
+//  * On the host, bgc_diag_mfma, bgc_diag_mfma_lowp and bgc_diag_mfma_classic are each a MatrixRun:
+//    the argument checks, the test plants (HostPlants), the per-CU bins (CuBins), the check launches
+//    and the warm-up / zero / timed rate launches in one place.  Each run says its limits, lists its
+//    launches and fills its own result struct.  with_plants picks between a kernel's production and
+//    planted instantiation.
 //  * bgc_diag_mfma_tile runs one round of the check in one wave (mfma_tile) and returns what every
 //    lane held, for the tests of the generated tiles.
 //  * bgc_diag_mfma_delayed and bgc_diag_burn_delayed make chosen waves of a throughput launch wait on
@@ -52,43 +55,10 @@ __device__ __forceinline__ int operand(uint32_t seed, uint32_t tile, int r, int 
 // Tile traits: a 16x16xkK MFMA on hash-derived operands.  Lane l holds its part of A row
 // (l & 15) and of B column (l & 15) from lane group l >> 4; the result lane l holds column
 // (l & 15) and, in element i of its accumulator (Acc, of Scalar), row row(l >> 4, i): 4 g + i, the
-// C/D map of every 16x16 MFMA but the fp64 one.  Lane is mfma_tile's per-lane record.  A element
-// (row, k) is operand(seed, tile, row, k, 0xA); B element (k, col) is b_operand(seed, tile, k, col).
+// C/D map of every 16x16 MFMA but the fp64 one.  Lane is mfma_tile's per-lane record.
 // mfma() takes the lane's two scale exponents, scale_exp() of its (row or column, lane group), and
 // expect() is the exact value of output element (row, col); a tile without block scales
 // ignores `scaled`.
-
-// v_mfma_f32_16x16x32_bf16: A is 16x32, B is 32x16, lane group g holds k = 8 g + j.
-struct Bf16Tile {
-  using Frag = bf16x8;
-  using Acc = f32x4;
-  using Scalar = float;
-  using Lane = bgc_tile_lane;
-  static constexpr int kK = 32;
-  static __device__ __forceinline__ int row(int g, int i) { return 4 * g + i; }
-  static_assert(kK <= kOperandStride, "operand() must tell every (row, k) and (k, column) apart");
-  static __device__ __forceinline__ Frag pack(uint32_t seed, uint32_t tile, int rc, int g, uint32_t which) {
-    Frag v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int o = which == 0xA ? operand(seed, tile, rc, 8 * g + j, 0xA) : b_operand(seed, tile, 8 * g + j, rc);
-      v[j] = static_cast<__bf16>(static_cast<float>(o));
-    }
-    return v;
-  }
-  static __device__ __forceinline__ f32x4 mfma(Frag a, Frag b, f32x4 acc, int /*sa*/, int /*sb*/) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int b_operand(uint32_t seed, uint32_t tile, int k, int col) {
-    return operand(seed, tile, k, col, 0xB);
-  }
-  static __device__ __forceinline__ int scale_exp(uint32_t, uint32_t, int, int, uint32_t, bool) { return 0; }
-  static __device__ __forceinline__ float expect(uint32_t seed, uint32_t tile, int row, int col, bool /*scaled*/) {
-    int dot = 0;
-    for (int k = 0; k < kK; ++k) dot += operand(seed, tile, row, k, 0xA) * b_operand(seed, tile, k, col);
-    return static_cast<float>(dot);
-  }
-};
 
 // Low-precision (MX block-scaled) matrix cores: v_mfma_scale_f32_16x16x128_f8f6f4.
 // Lane l holds 32 K-elements of A row (l & 15) and of B column (l & 15) from lane group
@@ -167,17 +137,29 @@ struct MxTile {
   }
 };
 
-// The classic matrix-core paths: fp16 (K 32), int8 (K 64), fp32 and fp64 (K 4).  A path says what
-// its MFMA takes and returns; ClassicTile below makes a tile trait of it.  Lane group g holds
-// k = kPerLane g + j in element j of its fragment, of A row rc and of B column rc (the one-hot
-// probes of tests/gpu/test_diag_classic.py read this layout and the row maps back through
-// classic_gemm).  wide() maps a hash to a check-phase operand as wide as the multipliers; the bounds
-// that keep every partial sum an exact integer are proved in gpu_diag.h.
+// The dense matrix-core paths: bf16 (K 32) and the classic fp16 (K 32), int8 (K 64), fp32 and fp64
+// (K 4).  A path says what its MFMA takes and returns and names mfma_tile's lane record; DenseTile
+// below makes a tile trait of it.  Lane group g holds k = kPerLane g + j in element j of its
+// fragment, of A row rc and of B column rc (the one-hot probes of tests/gpu/test_diag_classic.py
+// read this layout and the row maps back through dense_gemm).  A classic path's wide() maps a hash
+// to a check-phase operand as wide as the multipliers; the bounds that keep every partial sum an
+// exact integer are proved in gpu_diag.h.  bf16 has no wide check.
+struct Bf16Path {
+  using Elem = __bf16;
+  using Frag = bf16x8;
+  using Acc = f32x4;
+  using Sum = int;
+  using Lane = bgc_tile_lane;
+  static constexpr int kK = 32, kPerLane = 8;
+  static __device__ __forceinline__ int row(int g, int i) { return 4 * g + i; }
+  static __device__ __forceinline__ Acc mfma(Frag a, Frag b, Acc c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+};
 struct F16Path {
   using Elem = _Float16;
   using Frag = f16x8;
   using Acc = f32x4;
   using Sum = int;
+  using Lane = bgc_classic_tile_lane;
   static constexpr int kK = 32, kPerLane = 8;
   static __device__ __forceinline__ int wide(uint32_t h) { return static_cast<int>(h % 1025u) - 512; }
   static __device__ __forceinline__ int row(int g, int i) { return 4 * g + i; }
@@ -188,6 +170,7 @@ struct I8Path {
   using Frag = i8x16;
   using Acc = i32x4;
   using Sum = int;
+  using Lane = bgc_classic_tile_lane;
   static constexpr int kK = 64, kPerLane = 16;
   static __device__ __forceinline__ int wide(uint32_t h) { return static_cast<int8_t>(h & 0xffu); }
   static __device__ __forceinline__ int row(int g, int i) { return 4 * g + i; }
@@ -200,6 +183,7 @@ struct F32Path {
   using Frag = f32x1;
   using Acc = f32x4;
   using Sum = int;
+  using Lane = bgc_classic_tile_lane;
   static constexpr int kK = 4, kPerLane = 1;
   static __device__ __forceinline__ int wide(uint32_t h) { return static_cast<int>(h % 4095u) - 2047; }
   static __device__ __forceinline__ int row(int g, int i) { return 4 * g + i; }
@@ -211,25 +195,31 @@ struct F64Path {
   using Frag = f64x1;
   using Acc = f64x4;
   using Sum = long long;
+  using Lane = bgc_classic_tile_lane;
   static constexpr int kK = 4, kPerLane = 1;
   static __device__ __forceinline__ int wide(uint32_t h) { return static_cast<int>(h >> 6) - (1 << 25); }
   static __device__ __forceinline__ int row(int g, int i) { return g + 4 * i; }
   static __device__ __forceinline__ Acc mfma(Frag a, Frag b, Acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a[0], b[0], c, 0, 0, 0); }
 };
 
-// The tile of a classic path: A[row][k] and B[k][col] are indexed as the bf16 tile's, with values
-// wide() of the operand hash in the check (kWide) and {-1, 0, 1} in the throughput phase.
+// The tile of a dense path: A[row][k] = value(row, k, 0xA) and B[k][col] = value(k, col, 0xB), where
+// value is wide() of the operand hash in a classic path's check (kWide) and operand(), in {-1, 0, 1},
+// in the bf16 check and in every throughput phase.
 template <class Path, bool kWide>
-struct ClassicTile {
+struct DenseTile {
   using Frag = typename Path::Frag;
   using Acc = typename Path::Acc;
   using Scalar = std::remove_reference_t<decltype(Acc{}[0])>;
-  using Lane = bgc_classic_tile_lane;
+  using Lane = typename Path::Lane;
   static constexpr int kK = Path::kK;
   static_assert(kK <= kOperandStride, "operand() must tell every (row, k) and (k, column) apart");
   static __device__ __forceinline__ int row(int g, int i) { return Path::row(g, i); }
   static __device__ __forceinline__ int value(uint32_t seed, uint32_t tile, int r, int c, uint32_t which) {
-    return kWide ? Path::wide(operand_hash(seed, tile, r, c, which)) : operand(seed, tile, r, c, which);
+    if constexpr (kWide) {
+      return Path::wide(operand_hash(seed, tile, r, c, which));
+    } else {
+      return operand(seed, tile, r, c, which);
+    }
   }
   static __device__ __forceinline__ Frag pack(uint32_t seed, uint32_t tile, int rc, int g, uint32_t which) {
     Frag v;
@@ -251,6 +241,8 @@ struct ClassicTile {
     return static_cast<Scalar>(dot);
   }
 };
+
+using Bf16Tile = DenseTile<Bf16Path, false>;
 
 // Test plants (gpu_diag.h, "planted variants").  The check and throughput kernels end in a pack
 // `Plants... plants`: empty in the production instantiations, which so take no further argument and
@@ -465,37 +457,14 @@ __global__ __launch_bounds__(64) void mx_gemm(const uint8_t* __restrict__ A, con
   for (int i = 0; i < 4; ++i) C[static_cast<size_t>(m0 + 4 * g + i) * N + n0 + rc] = acc[i];
 }
 
-// Plain MFMA GEMM for the host cross-check: C[M,N] (fp32) = A[M,K] * B[K,N] (bf16,
-// row-major).  One wave per 16x16 output tile (grid N/16 x M/16), K consumed 32 at a time by
-// v_mfma_f32_16x16x32_bf16 with the same operand layout as the tests above: lane l
-// holds A row (l & 15) / B column (l & 15), k = 8 * (l >> 4) + j; the result lane l
-// holds column (l & 15), rows 4 * (l >> 4) + i.
-__global__ __launch_bounds__(64) void mfma_gemm(const __bf16* __restrict__ A, const __bf16* __restrict__ B,
-                                                float* __restrict__ C, int /*M*/, int N, int K) {
-  const int lane = threadIdx.x;
-  const int tm = blockIdx.y * 16, tn = blockIdx.x * 16;
-  const int rc = lane & 15, kb = 8 * (lane >> 4);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int k0 = 0; k0 < K; k0 += 32) {
-    bf16x8 a, b;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      a[j] = A[static_cast<size_t>(tm + rc) * K + k0 + kb + j];
-      b[j] = B[static_cast<size_t>(k0 + kb + j) * N + tn + rc];
-    }
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) C[static_cast<size_t>(tm + 4 * (lane >> 4) + i) * N + tn + rc] = acc[i];
-}
-
-// The same on a classic path: C[M,N] (double, which holds every path's results exactly) =
-// A[M,K] * B[K,N] in the path's element type, row-major.  One wave per 16x16 output tile (grid
-// N/16 x M/16), K consumed Path::kK at a time; lane l loads A row (l & 15) / B column (l & 15) at
-// k = kPerLane (l >> 4) + j straight from memory and writes rows Path::row(l >> 4, i).
-template <class Path>
-__global__ __launch_bounds__(64) void classic_gemm(const typename Path::Elem* __restrict__ A, const typename Path::Elem* __restrict__ B,
-                                                   double* __restrict__ C, int /*M*/, int N, int K) {
+// Plain MFMA GEMM on a dense path for the host cross-check: C[M,N] = A[M,K] * B[K,N] in the path's
+// element type, row-major; C is fp32 for bf16 and double, which holds every classic path's results
+// exactly, for those.  One wave per 16x16 output tile (grid N/16 x M/16), K consumed Path::kK at a
+// time with the same operand layout as the tests above: lane l loads A row (l & 15) / B column
+// (l & 15) at k = kPerLane (l >> 4) + j straight from memory and writes rows Path::row(l >> 4, i).
+template <class Path, class CElem>
+__global__ __launch_bounds__(64) void dense_gemm(const typename Path::Elem* __restrict__ A, const typename Path::Elem* __restrict__ B,
+                                                 CElem* __restrict__ C, int /*M*/, int N, int K) {
   const int lane = threadIdx.x;
   const int tm = blockIdx.y * 16, tn = blockIdx.x * 16;
   const int rc = lane & 15, g = lane >> 4, kb = Path::kPerLane * g;
@@ -510,27 +479,35 @@ __global__ __launch_bounds__(64) void classic_gemm(const typename Path::Elem* __
     acc = Path::mfma(a, b, acc);
   }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) C[static_cast<size_t>(tm + Path::row(g, i)) * N + tn + rc] = static_cast<double>(acc[i]);
+  for (int i = 0; i < 4; ++i) C[static_cast<size_t>(tm + Path::row(g, i)) * N + tn + rc] = static_cast<CElem>(acc[i]);
 }
 
 // `f(Path{})` for classic path 0..3 (BGC_CLASSIC_*)
 template <class F>
-void with_classic_path(int path, F&& f) {
+auto with_classic_path(int path, F&& f) {
   switch (path) {
-    case BGC_CLASSIC_FP16: f(F16Path{}); break;
-    case BGC_CLASSIC_INT8: f(I8Path{}); break;
-    case BGC_CLASSIC_FP32: f(F32Path{}); break;
-    default: f(F64Path{}); break;
+    case BGC_CLASSIC_FP16: return f(F16Path{});
+    case BGC_CLASSIC_INT8: return f(I8Path{});
+    case BGC_CLASSIC_FP32: return f(F32Path{});
+    default: return f(F64Path{});
   }
 }
 
 // `f(std::integral_constant<int, kFmt>)` for MX format 0 (fp8 e4m3) or 4 (fp4 e2m1)
 template <class F>
-void with_mx_fmt(int fmt, F&& f) {
-  if (fmt == 0) {
-    f(std::integral_constant<int, 0>{});
-  } else {
-    f(std::integral_constant<int, 4>{});
+auto with_mx_fmt(int fmt, F&& f) {
+  if (fmt == 0) return f(std::integral_constant<int, 0>{});
+  return f(std::integral_constant<int, 4>{});
+}
+
+// `f(Tile{}, kTimed)` for a burn dtype (BGC_BURN_*): the bf16 rate kernel times its waves per XCC,
+// the MX ones do not
+template <class F>
+auto with_burn_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case BGC_BURN_BF16: return f(Bf16Tile{}, std::true_type{});
+    case BGC_BURN_FP8: return f(MxTile<0>{}, std::false_type{});
+    default: return f(MxTile<4>{}, std::false_type{});
   }
 }
 
@@ -552,30 +529,12 @@ void launch_check(int blocks, uint32_t seed, int rounds, int scaled, unsigned* c
   });
 }
 
-template <class Tile>
-void launch_tile(uint32_t seed, uint32_t tile, int scaled, typename Tile::Lane* lanes) {
-  hipLaunchKernelGGL(mfma_tile<Tile>, dim3(1), dim3(64), 0, nullptr, seed, tile, scaled, lanes);
-}
-
 template <class Tile, bool kTimed, class P>
 void launch_rate(int blocks, uint32_t seed, int iters, unsigned* fails, unsigned long long* xt, unsigned* xw, PlantList<P> plants) {
   with_plants(plants, [&](auto... pl) {
     hipLaunchKernelGGL((mfma_throughput<Tile, kTimed, decltype(pl)...>), dim3(blocks), dim3(kBlock), 0, nullptr, seed, iters, fails,
                        xt, xw, pl...);
   });
-}
-
-// one throughput launch of a burn dtype: bf16 (timed per XCC into xt / xw) or MX fp8 / fp4; the
-// plants are value plants (RatePlants) or delay plants (DelayPlants)
-template <class P = bgc_mfma_rate_plant>
-void launch_throughput(int dtype, int blocks, uint32_t seed, int iters, unsigned* fails, unsigned long long* xt = nullptr,
-                       unsigned* xw = nullptr, PlantList<P> plants = {}) {
-  if (dtype == BGC_BURN_BF16) {
-    launch_rate<Bf16Tile, true>(blocks, seed, iters, fails, xt, xw, plants);
-  } else {
-    with_mx_fmt(dtype == BGC_BURN_FP8 ? 0 : 4,
-                [&](auto fmt) { launch_rate<MxTile<decltype(fmt)::value>, false>(blocks, seed, iters, fails, xt, xw, plants); });
-  }
 }
 
 // waves of `waves_per_cu` per CU as kBlock-thread blocks
@@ -604,13 +563,14 @@ template <class At>
 struct HostPlants {
   std::vector<At> host[4];
   DeviceBuffer dev[4];
-  // Before the device is touched: false unless the list, every plant's launch (< launches) and its place (ok) are valid.
+  // Before the device is touched: false unless the list, every plant's launch (< launches) and its place
+  // in it (ok(launch, place)) are valid.
   template <class P, class Ok>
   bool take(const P* plants, int n, int launches, Ok&& ok) {
     if (!plant_list_ok(plants, n)) return false;
     for (int j = 0; j < n; ++j) {
       const auto [launch, at] = split(plants[j]);
-      if (launch < 0 || launch >= launches || !ok(at)) return false;
+      if (launch < 0 || launch >= launches || !ok(launch, at)) return false;
       host[launch].push_back(at);
     }
     return true;
@@ -668,10 +628,7 @@ struct CuBins {
       if (!seen) continue;
       out->cus_seen++;
       if (xcc_mask) *xcc_mask |= 1u << ((k >> 8) & 7);
-      if (bad_here) {
-        if (out->bad_cus < 64) out->bad_cu_keys[out->bad_cus] = k;
-        out->bad_cus++;
-      }
+      if (bad_here) note_bad_cu(out, k);
     }
     return 0;
   }
@@ -682,59 +639,118 @@ template <class Tile>
 double rate_flops(int blocks, int iters) {
   return static_cast<double>(blocks) * (kBlock / 64) * iters * 4.0 * (2.0 * 16 * 16 * Tile::kK);
 }
+double tera_per_s(double flops, float ms) { return ms > 0 ? flops / (ms * 1e-3) / 1e12 : 0.0; }
+
+// Per-XCC bins of a timed (kTimed) throughput launch: the waves that ran on each XCC and the sum of their ticks.
+struct XccBins {
+  DeviceBuffer ticks, waves;
+  int alloc() {
+    HIP_TRY(ticks.alloc(8 * sizeof(unsigned long long)));
+    HIP_TRY(waves.alloc(8 * sizeof(unsigned)));
+    return 0;
+  }
+  int zero() const {
+    HIP_TRY(hipMemset(ticks.p, 0, 8 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(waves.p, 0, 8 * sizeof(unsigned)));
+    return 0;
+  }
+  unsigned long long* t() const { return ticks.as<unsigned long long>(); }
+  unsigned* w() const { return waves.as<unsigned>(); }
+};
+
+bool any_delta(int /*launch*/, float /*delta*/) { return true; }
+
+// What bgc_diag_mfma, bgc_diag_mfma_lowp and bgc_diag_mfma_classic share: kChecks check launches and up to
+// four rate launches on the null stream, every launch with its own test plants.
+template <int kChecks>
+struct MatrixRun {
+  const uint32_t seed;
+  const int rounds;  // tiles per wave of a check launch
+  int blocks = 0;
+  HostPlants<bgc_mfma_check_plant> check_plants;  // by check launch
+  HostPlants<bgc_mfma_rate_plant> rate_plants;    // by rate launch
+  CuBins<kChecks> bins;                           // by check launch
+  DeviceBuffer fails;                             // wrong accumulator elements, one word per rate launch
+  Events ev;
+
+  MatrixRun(uint32_t seed_, int rounds_) : seed(seed_), rounds(rounds_) {}
+
+  // All that comes before the first launch.  Refuses with "invalid arguments" before the device is touched
+  // unless the caller's own limits hold (limits_ok) and every plant names a launch, a place in it and, for
+  // delta_ok(launch, delta), a delta that are valid; then clears *out, sizes the launches, uploads the
+  // plants (refusing one in a wave beyond the launch) and allocates the bins, the counters and the events.
+  template <class Result, class CheckPlant, class RatePlant>
+  int begin(Result* out, bool limits_ok, int device, int waves_per_cu, const CheckPlant* check, int n_check, const RatePlant* rate,
+            int n_rate, int rate_launches, bool (*delta_ok)(int, float) = any_delta) {
+    if (!(out && limits_ok &&
+          check_plants.take(check, n_check, kChecks,
+                            [&](int l, const auto& at) { return check_plant_ok(at, rounds) && delta_ok(l, at.delta); }) &&
+          rate_plants.take(rate, n_rate, rate_launches, [&](int l, const auto& at) { return rate_plant_ok(at) && delta_ok(l, at.delta); }))) {
+      g_last_error = "invalid arguments";
+      return 1;
+    }
+    std::memset(out, 0, sizeof(*out));
+    HIP_TRY(hipSetDevice(device));
+    blocks = wave_blocks(device, waves_per_cu);
+    if (check_plants.upload(blocks) != 0 || rate_plants.upload(blocks) != 0 || bins.alloc() != 0) return 1;
+    HIP_TRY(fails.alloc(4 * sizeof(unsigned), true));
+    HIP_TRY(ev.create());
+    return 0;
+  }
+
+  // check launch `launch`, into its slice of the bins; the caller puts its check launches in one timed window
+  template <class Tile>
+  void check(int launch, int scaled) const {
+    launch_check<Tile>(blocks, seed, rounds, scaled, bins.tiles_of(launch), bins.bad_of(launch), check_plants.of(launch));
+  }
+
+  // Rate launch `launch`: after a warm-up launch of 64 iterations without plants and with the counters it
+  // wrote zeroed again (if warm_up), the launch of `iters` iterations with `plants`, alone in a timed
+  // window (*ms).  A kTimed launch bins its waves in *xcc.
+  template <class Tile, bool kTimed, class P>
+  int rate(int launch, int iters, bool warm_up, PlantList<P> plants, float* ms, const XccBins* xcc = nullptr) const {
+    unsigned* f = fails.as<unsigned>() + launch;
+    unsigned long long* xt = xcc ? xcc->t() : nullptr;
+    unsigned* xw = xcc ? xcc->w() : nullptr;
+    if (warm_up) {
+      launch_rate<Tile, kTimed>(blocks, seed, 64, f, xt, xw, RatePlants{});
+      HIP_TRY(hipMemset(f, 0, sizeof(unsigned)));
+      if (xcc && xcc->zero() != 0) return 1;
+    }
+    return timed(ev, ms, [&] { launch_rate<Tile, kTimed>(blocks, seed, iters, f, xt, xw, plants); });
+  }
+
+  // after the last launch: whether every rate launch's accumulators matched
+  int throughput_ok(int* ok) const {
+    unsigned h[4];
+    HIP_TRY(hipMemcpy(h, fails.p, sizeof(h), hipMemcpyDeviceToHost));
+    *ok = (h[0] | h[1] | h[2] | h[3]) == 0;
+    return 0;
+  }
+};
 
 int mfma_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_mfma_check_plant* check, int n_check,
              const bgc_mfma_rate_plant* rate, int n_rate, const bgc_mfma_delay_plant* delays, int n_delay, bgc_mfma_result* out) {
-  const int rounds = BGC_MFMA_CHECK_ROUNDS;
-  HostPlants<bgc_mfma_check_plant> check_plants;
-  HostPlants<bgc_mfma_rate_plant> rate_plants;
+  MatrixRun<1> run(seed, BGC_MFMA_CHECK_ROUNDS);
   HostPlants<bgc_mfma_delay_plant> delay_plants;  // no entry point takes both these and rate plants
-  if (!(out && waves_per_cu > 0 && throughput_iters > 0 && throughput_iters <= (1 << 18) &&
-        check_plants.take(check, n_check, 1, [&](const auto& at) { return check_plant_ok(at, rounds); }) &&
-        rate_plants.take(rate, n_rate, 1, rate_plant_ok) && delay_plants.take(delays, n_delay, 1, delay_plant_ok))) {
-    g_last_error = "invalid arguments";
+  XccBins xcc;
+  const bool limits_ok = waves_per_cu > 0 && throughput_iters > 0 && throughput_iters <= (1 << 18) &&
+                         delay_plants.take(delays, n_delay, 1, [](int, const auto& at) { return delay_plant_ok(at); });
+  if (run.begin(out, limits_ok, device, waves_per_cu, check, n_check, rate, n_rate, 1) != 0 || delay_plants.upload(run.blocks) != 0 ||
+      xcc.alloc() != 0) {
     return 1;
   }
-  std::memset(out, 0, sizeof(*out));
-  HIP_TRY(hipSetDevice(device));
-  const int blocks = wave_blocks(device, waves_per_cu);
-  if (check_plants.upload(blocks) != 0 || rate_plants.upload(blocks) != 0 || delay_plants.upload(blocks) != 0) return 1;
-  CuBins<1> bins;
-  if (bins.alloc() != 0) return 1;
-  DeviceBuffer fails, xticks, xwaves;
-  HIP_TRY(fails.alloc(sizeof(unsigned)));
-  HIP_TRY(xticks.alloc(8 * sizeof(unsigned long long)));
-  HIP_TRY(xwaves.alloc(8 * sizeof(unsigned)));
-  Events ev;
-  HIP_TRY(ev.create());
   float ms_check = 0.f, ms_tp = 0.f;
-  if (timed(ev, &ms_check, [&] {
-        launch_check<Bf16Tile>(blocks, seed, rounds, 0, bins.tiles_of(0), bins.bad_of(0), check_plants.of(0));
-      }) != 0) {
+  if (timed(run.ev, &ms_check, [&] { run.check<Bf16Tile>(0, 0); }) != 0) return 1;
+  // warm-up, then the timed throughput launch with the delay plants or the value plants
+  if ((n_delay > 0 ? run.rate<Bf16Tile, true>(0, throughput_iters, true, delay_plants.of(0), &ms_tp, &xcc)
+                   : run.rate<Bf16Tile, true>(0, throughput_iters, true, run.rate_plants.of(0), &ms_tp, &xcc)) != 0) {
     return 1;
   }
-  // warm-up then timed throughput pass
-  auto* xt = xticks.as<unsigned long long>();
-  auto* xw = xwaves.as<unsigned>();
-  launch_throughput(BGC_BURN_BF16, blocks, seed, 64, fails.as<unsigned>(), xt, xw);
-  HIP_TRY(hipMemset(fails.p, 0, sizeof(unsigned)));
-  HIP_TRY(hipMemset(xticks.p, 0, 8 * sizeof(unsigned long long)));
-  HIP_TRY(hipMemset(xwaves.p, 0, 8 * sizeof(unsigned)));
-  if (timed(ev, &ms_tp, [&] {
-        if (n_delay > 0) {
-          launch_throughput(BGC_BURN_BF16, blocks, seed, throughput_iters, fails.as<unsigned>(), xt, xw, delay_plants.of(0));
-        } else {
-          launch_throughput(BGC_BURN_BF16, blocks, seed, throughput_iters, fails.as<unsigned>(), xt, xw, rate_plants.of(0));
-        }
-      }) != 0) {
-    return 1;
-  }
-  unsigned h_fails = 0;
-  HIP_TRY(hipMemcpy(&h_fails, fails.p, sizeof(unsigned), hipMemcpyDeviceToHost));
   unsigned long long h_ticks[8];
   unsigned h_waves[8];
-  HIP_TRY(hipMemcpy(h_ticks, xticks.p, sizeof(h_ticks), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(h_waves, xwaves.p, sizeof(h_waves), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h_ticks, xcc.ticks.p, sizeof(h_ticks), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h_waves, xcc.waves.p, sizeof(h_waves), hipMemcpyDeviceToHost));
   int rate_khz = 0;
   if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || rate_khz <= 0) {
     rate_khz = 100000;  // CDNA constant clock: 100 MHz
@@ -749,68 +765,41 @@ int mfma_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, 
   }
   out->xcc_balance = hi > 0 ? lo / hi : 0.0;
   unsigned xcc_mask = 0;
-  if (bins.fold(out, {&out->mismatches}, &xcc_mask) != 0) return 1;
+  if (run.bins.fold(out, {&out->mismatches}, &xcc_mask) != 0 || run.throughput_ok(&out->throughput_ok) != 0) return 1;
   out->xccs_seen = __builtin_popcount(xcc_mask);
-  out->tflops = rate_flops<Bf16Tile>(blocks, throughput_iters) / (ms_tp * 1e-3) / 1e12;
-  out->throughput_ok = h_fails == 0;
+  out->tflops = rate_flops<Bf16Tile>(run.blocks, throughput_iters) / (ms_tp * 1e-3) / 1e12;
   out->elapsed_ms = ms_check + ms_tp;
   return 0;
 }
 
 int lowp_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_lowp_check_plant* check, int n_check,
              const bgc_lowp_rate_plant* rate, int n_rate, bgc_lowp_result* out) {
-  const int rounds = BGC_LOWP_CHECK_ROUNDS;
   // launches: check variant (0 fp8, 1 fp8 scaled, 2 fp4, 3 fp4 scaled), rate format (0 fp8, 1 fp4)
-  HostPlants<bgc_mfma_check_plant> check_plants;
-  HostPlants<bgc_mfma_rate_plant> rate_plants;
-  if (!(out && waves_per_cu > 0 && waves_per_cu <= 64 && throughput_iters > 0 && throughput_iters <= (1 << 16) &&
-        check_plants.take(check, n_check, 4, [&](const auto& at) { return check_plant_ok(at, rounds); }) &&
-        rate_plants.take(rate, n_rate, 2, rate_plant_ok))) {
-    g_last_error = "invalid arguments";
-    return 1;
-  }
-  std::memset(out, 0, sizeof(*out));
-  HIP_TRY(hipSetDevice(device));
-  const int blocks = wave_blocks(device, waves_per_cu);
-  if (check_plants.upload(blocks) != 0 || rate_plants.upload(blocks) != 0) return 1;
-  CuBins<4> bins;  // by check variant
-  if (bins.alloc() != 0) return 1;
-  DeviceBuffer fails;
-  HIP_TRY(fails.alloc(2 * sizeof(unsigned)));
-  auto* f = fails.as<unsigned>();
-  Events ev;
-  HIP_TRY(ev.create());
-  float total = 0.f;
-  if (timed(ev, &total, [&] {
+  MatrixRun<4> run(seed, BGC_LOWP_CHECK_ROUNDS);
+  const bool limits_ok = waves_per_cu > 0 && waves_per_cu <= 64 && throughput_iters > 0 && throughput_iters <= (1 << 16);
+  if (run.begin(out, limits_ok, device, waves_per_cu, check, n_check, rate, n_rate, 2) != 0) return 1;
+  float ms_check = 0.f, ms_fmt[2] = {0.f, 0.f};
+  if (timed(run.ev, &ms_check, [&] {
         for (int sc = 0; sc < 2; ++sc) {
-          launch_check<MxTile<0>>(blocks, seed, rounds, sc, bins.tiles_of(sc), bins.bad_of(sc), check_plants.of(sc));
-          launch_check<MxTile<4>>(blocks, seed, rounds, sc, bins.tiles_of(2 + sc), bins.bad_of(2 + sc), check_plants.of(2 + sc));
+          run.check<MxTile<0>>(sc, sc);
+          run.check<MxTile<4>>(2 + sc, sc);
         }
       }) != 0) {
     return 1;
   }
-  // warm-up, then one timed launch per format
-  launch_throughput(BGC_BURN_FP8, blocks, seed, 64, f);
-  HIP_TRY(hipMemset(f, 0, 2 * sizeof(unsigned)));
-  float ms_fmt[2] = {0.f, 0.f};
-  for (int i = 0; i < 2; ++i) {
-    if (timed(ev, &ms_fmt[i], [&] {
-          launch_throughput(i == 0 ? BGC_BURN_FP8 : BGC_BURN_FP4, blocks, seed, throughput_iters, f + i, nullptr, nullptr, rate_plants.of(i));
-        }) != 0) {
-      return 1;
-    }
-    total += ms_fmt[i];
-  }
-  unsigned h_f[2] = {0, 0};
-  HIP_TRY(hipMemcpy(h_f, f, sizeof(h_f), hipMemcpyDeviceToHost));
-  if (bins.fold(out, {&out->fp8_mismatches, &out->fp8_scaled_mismatches, &out->fp4_mismatches, &out->fp4_scaled_mismatches}) != 0) {
+  // one fp8 warm-up for both formats, then one timed launch per format
+  if (run.rate<MxTile<0>, false>(0, throughput_iters, true, run.rate_plants.of(0), &ms_fmt[0]) != 0 ||
+      run.rate<MxTile<4>, false>(1, throughput_iters, false, run.rate_plants.of(1), &ms_fmt[1]) != 0) {
     return 1;
   }
-  const double flops = rate_flops<MxTile<0>>(blocks, throughput_iters);  // the same for fp4
-  out->fp8_tflops = ms_fmt[0] > 0 ? flops / (ms_fmt[0] * 1e-3) / 1e12 : 0.0;
-  out->fp4_tflops = ms_fmt[1] > 0 ? flops / (ms_fmt[1] * 1e-3) / 1e12 : 0.0;
-  out->throughput_ok = h_f[0] == 0 && h_f[1] == 0;
-  out->elapsed_ms = total;
+  if (run.bins.fold(out, {&out->fp8_mismatches, &out->fp8_scaled_mismatches, &out->fp4_mismatches, &out->fp4_scaled_mismatches}) != 0 ||
+      run.throughput_ok(&out->throughput_ok) != 0) {
+    return 1;
+  }
+  const double flops = rate_flops<MxTile<0>>(run.blocks, throughput_iters);  // the same for fp4
+  out->fp8_tflops = tera_per_s(flops, ms_fmt[0]);
+  out->fp4_tflops = tera_per_s(flops, ms_fmt[1]);
+  out->elapsed_ms = ms_check + ms_fmt[0] + ms_fmt[1];
   return 0;
 }
 
@@ -819,75 +808,42 @@ bool classic_delta_ok(int path, float delta) {
   return path != BGC_CLASSIC_INT8 || (std::isfinite(delta) && delta == std::trunc(delta) && std::fabs(delta) < 2147483648.f);
 }
 
-// one path's warm-up launch and timed throughput launch: its device time, and its failures in *fails
-template <class Path>
-int classic_rate(const Events& ev, int blocks, uint32_t seed, int iters, unsigned* fails, RatePlants plants, float* ms) {
-  using Tile = ClassicTile<Path, false>;
-  launch_rate<Tile, false>(blocks, seed, 64, fails, nullptr, nullptr, RatePlants{});
-  HIP_TRY(hipMemset(fails, 0, sizeof(unsigned)));
-  return timed(ev, ms, [&] { launch_rate<Tile, false>(blocks, seed, iters, fails, nullptr, nullptr, plants); });
-}
-
 int classic_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, const bgc_lowp_check_plant* check, int n_check,
                 const bgc_lowp_rate_plant* rate, int n_rate, bgc_classic_result* out) {
-  const int rounds = BGC_CLASSIC_CHECK_ROUNDS;
   // launches: one check and one rate launch per path (BGC_CLASSIC_*)
-  HostPlants<bgc_mfma_check_plant> check_plants;
-  HostPlants<bgc_mfma_rate_plant> rate_plants;
-  bool ok = out && waves_per_cu > 0 && waves_per_cu <= 64 && throughput_iters > 0 && throughput_iters <= (1 << 16) &&
-            check_plants.take(check, n_check, 4, [&](const auto& at) { return check_plant_ok(at, rounds); }) &&
-            rate_plants.take(rate, n_rate, 4, rate_plant_ok);
-  for (int j = 0; ok && j < n_check; ++j) ok = classic_delta_ok(check[j].variant, check[j].at.delta);
-  for (int j = 0; ok && j < n_rate; ++j) ok = classic_delta_ok(rate[j].fmt, rate[j].at.delta);
-  if (!ok) {
-    g_last_error = "invalid arguments";
-    return 1;
-  }
-  std::memset(out, 0, sizeof(*out));
-  HIP_TRY(hipSetDevice(device));
-  const int blocks = wave_blocks(device, waves_per_cu);
-  if (check_plants.upload(blocks) != 0 || rate_plants.upload(blocks) != 0) return 1;
-  CuBins<4> bins;  // by path
-  if (bins.alloc() != 0) return 1;
-  DeviceBuffer fails;
-  HIP_TRY(fails.alloc(4 * sizeof(unsigned), true));
-  auto* f = fails.as<unsigned>();
-  Events ev;
-  HIP_TRY(ev.create());
+  MatrixRun<4> run(seed, BGC_CLASSIC_CHECK_ROUNDS);
+  const bool limits_ok = waves_per_cu > 0 && waves_per_cu <= 64 && throughput_iters > 0 && throughput_iters <= (1 << 16);
+  if (run.begin(out, limits_ok, device, waves_per_cu, check, n_check, rate, n_rate, 4, classic_delta_ok) != 0) return 1;
   float total = 0.f;
-  if (timed(ev, &total, [&] {
+  if (timed(run.ev, &total, [&] {
         for (int p = 0; p < 4; ++p) {
-          with_classic_path(p, [&](auto path) {
-            launch_check<ClassicTile<decltype(path), true>>(blocks, seed, rounds, 0, bins.tiles_of(p), bins.bad_of(p), check_plants.of(p));
-          });
+          with_classic_path(p, [&](auto path) { run.check<DenseTile<decltype(path), true>>(p, 0); });
         }
       }) != 0) {
     return 1;
   }
   // per path: a warm-up launch, then one timed launch
   for (int p = 0; p < 4; ++p) {
-    int rc = 0;
     float ms = 0.f;
     double flops = 0;
-    with_classic_path(p, [&](auto path) {
-      rc = classic_rate<decltype(path)>(ev, blocks, seed, throughput_iters, f + p, rate_plants.of(p), &ms);
-      flops = rate_flops<ClassicTile<decltype(path), false>>(blocks, throughput_iters);
+    const int rc = with_classic_path(p, [&](auto path) {
+      using Tile = DenseTile<decltype(path), false>;
+      flops = rate_flops<Tile>(run.blocks, throughput_iters);
+      return run.rate<Tile, false>(p, throughput_iters, true, run.rate_plants.of(p), &ms);
     });
     if (rc != 0) return 1;
     out->rate_ms[p] = ms;
-    out->rate[p] = ms > 0 ? flops / (ms * 1e-3) / 1e12 : 0.0;
+    out->rate[p] = tera_per_s(flops, ms);
     total += ms;
   }
-  unsigned h_f[4] = {0, 0, 0, 0};
-  HIP_TRY(hipMemcpy(h_f, f, sizeof(h_f), hipMemcpyDeviceToHost));
   int path_cus[4] = {0, 0, 0, 0};
-  if (bins.fold(out, {&out->mismatches[0], &out->mismatches[1], &out->mismatches[2], &out->mismatches[3]}, nullptr, path_cus) != 0) {
+  if (run.bins.fold(out, {&out->mismatches[0], &out->mismatches[1], &out->mismatches[2], &out->mismatches[3]}, nullptr, path_cus) != 0 ||
+      run.throughput_ok(&out->throughput_ok) != 0) {
     return 1;
   }
   // Consecutive launches need not land on the same CUs, so the union over the paths says nothing about
   // one path: report the coverage that every path reached.
   out->cus_seen = *std::min_element(path_cus, path_cus + 4);
-  out->throughput_ok = h_f[0] == 0 && h_f[1] == 0 && h_f[2] == 0 && h_f[3] == 0;
   out->elapsed_ms = total;
   return 0;
 }
@@ -909,27 +865,25 @@ int burn_run(int device, int duration_ms, int waves_per_cu, uint32_t seed, int d
     delay_plants.host[0].push_back({BGC_PLANT_ALL_WAVES, ticks});
     if (delay_plants.upload(blocks) != 0) return 1;
   }
-  DeviceBuffer fails, xticks, xwaves;
+  DeviceBuffer fails;
+  XccBins xcc;  // the bf16 kernel writes them; the burn does not read them
   HIP_TRY(fails.alloc(sizeof(unsigned), true));
-  HIP_TRY(xticks.alloc(8 * sizeof(unsigned long long)));
-  HIP_TRY(xwaves.alloc(8 * sizeof(unsigned)));
+  if (xcc.alloc() != 0) return 1;
   Events ev, total;
   HIP_TRY(ev.create());
   HIP_TRY(total.create());
   // size one launch to ~10 ms at MI355X rates (iters * 4 MFMA per wave), measured below
   int iters = 2048;
-  const double flops_per_iter = dtype == BGC_BURN_BF16 ? rate_flops<Bf16Tile>(blocks, 1) : rate_flops<MxTile<0>>(blocks, 1);
+  const double flops_per_iter = with_burn_dtype(dtype, [&](auto tile, auto) { return rate_flops<decltype(tile)>(blocks, 1); });
   float ms = 0.f;
   HIP_TRY(hipEventRecord(total.a, nullptr));
   double sum_flops = 0;
   while (true) {
+    const DelayPlants delays = ticks > 0 && out->launches >= first_delayed_launch ? delay_plants.of(0) : DelayPlants{};
     if (timed(ev, &ms, [&] {
-          if (ticks > 0 && out->launches >= first_delayed_launch) {
-            launch_throughput(dtype, blocks, seed, iters, fails.as<unsigned>(), xticks.as<unsigned long long>(), xwaves.as<unsigned>(),
-                              delay_plants.of(0));
-          } else {
-            launch_throughput(dtype, blocks, seed, iters, fails.as<unsigned>(), xticks.as<unsigned long long>(), xwaves.as<unsigned>());
-          }
+          with_burn_dtype(dtype, [&](auto tile, auto timed_per_xcc) {
+            launch_rate<decltype(tile), decltype(timed_per_xcc)::value>(blocks, seed, iters, fails.as<unsigned>(), xcc.t(), xcc.w(), delays);
+          });
         }) != 0) {
       return 1;
     }
@@ -958,6 +912,36 @@ int burn_run(int device, int duration_ms, int waves_per_cu, uint32_t seed, int d
   out->mismatches = h_fails;
   out->tflops_mean = sum_flops / (out->elapsed_ms * 1e-3) / 1e12;
   return 0;
+}
+
+// mfma_tile<Tile> by one wave: what its 64 lanes held, to lanes[0..63]
+template <class Tile>
+int tile_run(int device, uint32_t seed, uint32_t tile, int scaled, typename Tile::Lane* lanes) {
+  using Lane = typename Tile::Lane;
+  HIP_TRY(hipSetDevice(device));
+  DeviceBuffer d;
+  HIP_TRY(d.alloc(64 * sizeof(Lane), true));
+  hipLaunchKernelGGL(mfma_tile<Tile>, dim3(1), dim3(64), 0, nullptr, seed, tile, scaled, d.as<Lane>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(lanes, d.p, 64 * sizeof(Lane), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// dense_gemm<Path> on host operands, or `refusal` as the last error unless M and N are multiples of 16
+// up to 4096 and K a multiple of the path's K up to 8192
+template <class Path, class CElem>
+int gemm_run(int device, int m, int n, int k, const void* a, const void* b, CElem* c, const char* refusal) {
+  using Elem = typename Path::Elem;
+  if (!a || !b || !c || m <= 0 || n <= 0 || k <= 0 || m % 16 || n % 16 || k % Path::kK || m > 4096 || n > 4096 || k > 8192) {
+    g_last_error = refusal;
+    return 1;
+  }
+  HIP_TRY(hipSetDevice(device));
+  const size_t a_bytes = static_cast<size_t>(m) * k * sizeof(Elem), b_bytes = static_cast<size_t>(k) * n * sizeof(Elem);
+  return gemm_on_host_operands({{a, a_bytes}, {b, b_bytes}}, c, static_cast<size_t>(m) * n, [&](const void* const* d, CElem* dc) {
+    hipLaunchKernelGGL((dense_gemm<Path, CElem>), dim3(n / 16, m / 16), dim3(64), 0, nullptr, static_cast<const Elem*>(d[0]),
+                       static_cast<const Elem*>(d[1]), dc, m, n, k);
+  });
 }
 
 }  // namespace
@@ -1001,33 +985,17 @@ int bgc_diag_mfma_classic_tile(int device, int path, uint32_t seed, uint32_t til
     g_last_error = "invalid arguments";
     return 1;
   }
-  HIP_TRY(hipSetDevice(device));
-  DeviceBuffer d;
-  HIP_TRY(d.alloc(64 * sizeof(bgc_classic_tile_lane), true));
-  with_classic_path(path, [&](auto p) { launch_tile<ClassicTile<decltype(p), true>>(seed, tile, 0, d.as<bgc_classic_tile_lane>()); });
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(lanes, d.p, 64 * sizeof(bgc_classic_tile_lane), hipMemcpyDeviceToHost));
-  return 0;
+  return with_classic_path(path, [&](auto p) { return tile_run<DenseTile<decltype(p), true>>(device, seed, tile, 0, lanes); });
 }
 
 int bgc_diag_gemm_dtype(int device, int path, int m, int n, int k, const void* a, const void* b, double* c) {
-  static const int kPathK[4] = {F16Path::kK, I8Path::kK, F32Path::kK, F64Path::kK};
-  static const size_t kElemBytes[4] = {sizeof(F16Path::Elem), sizeof(I8Path::Elem), sizeof(F32Path::Elem), sizeof(F64Path::Elem)};
-  if (!a || !b || !c || path < BGC_CLASSIC_FP16 || path > BGC_CLASSIC_FP64 || m <= 0 || n <= 0 || k <= 0 || m % 16 || n % 16 ||
-      k % kPathK[path] || m > 4096 || n > 4096 || k > 8192) {
-    g_last_error = "invalid arguments (path 0..3; M, N multiples of 16 up to 4096; K a multiple of the path's K up to 8192)";
+  static const char* const kRefusal =
+      "invalid arguments (path 0..3; M, N multiples of 16 up to 4096; K a multiple of the path's K up to 8192)";
+  if (path < BGC_CLASSIC_FP16 || path > BGC_CLASSIC_FP64) {
+    g_last_error = kRefusal;
     return 1;
   }
-  HIP_TRY(hipSetDevice(device));
-  const size_t a_bytes = static_cast<size_t>(m) * k * kElemBytes[path], b_bytes = static_cast<size_t>(k) * n * kElemBytes[path];
-  return gemm_on_host_operands({{a, a_bytes}, {b, b_bytes}}, c, static_cast<size_t>(m) * n, [&](const void* const* d, double* dc) {
-    with_classic_path(path, [&](auto p) {
-      using Path = decltype(p);
-      using Elem = typename Path::Elem;
-      hipLaunchKernelGGL(classic_gemm<Path>, dim3(n / 16, m / 16), dim3(64), 0, nullptr, static_cast<const Elem*>(d[0]),
-                         static_cast<const Elem*>(d[1]), dc, m, n, k);
-    });
-  });
+  return with_classic_path(path, [&](auto p) { return gemm_run<decltype(p)>(device, m, n, k, a, b, c, kRefusal); });
 }
 
 int bgc_diag_mfma_tile(int device, int path, int scaled, uint32_t seed, uint32_t tile, bgc_tile_lane* lanes) {
@@ -1035,18 +1003,9 @@ int bgc_diag_mfma_tile(int device, int path, int scaled, uint32_t seed, uint32_t
     g_last_error = "invalid arguments";
     return 1;
   }
-  HIP_TRY(hipSetDevice(device));
-  DeviceBuffer d;
-  HIP_TRY(d.alloc(64 * sizeof(bgc_tile_lane), true));
-  if (path == BGC_TILE_BF16) {
-    launch_tile<Bf16Tile>(seed, tile, scaled, d.as<bgc_tile_lane>());
-  } else {
-    with_mx_fmt(path == BGC_TILE_FP8 ? 0 : 4,
-                [&](auto fmt) { launch_tile<MxTile<decltype(fmt)::value>>(seed, tile, scaled, d.as<bgc_tile_lane>()); });
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(lanes, d.p, 64 * sizeof(bgc_tile_lane), hipMemcpyDeviceToHost));
-  return 0;
+  if (path == BGC_TILE_BF16) return tile_run<Bf16Tile>(device, seed, tile, scaled, lanes);
+  return with_mx_fmt(path == BGC_TILE_FP8 ? 0 : 4,
+                     [&](auto fmt) { return tile_run<MxTile<decltype(fmt)::value>>(device, seed, tile, scaled, lanes); });
 }
 
 int bgc_diag_burn(int device, int duration_ms, int waves_per_cu, uint32_t seed, bgc_burn_result* out) {
@@ -1067,18 +1026,8 @@ int bgc_diag_burn_delayed(int device, int duration_ms, int waves_per_cu, uint32_
 }
 
 int bgc_diag_gemm(int device, int m, int n, int k, const uint16_t* a_bf16, const uint16_t* b_bf16, float* c) {
-  if (!a_bf16 || !b_bf16 || !c || m <= 0 || n <= 0 || k <= 0 || m % 16 || n % 16 || k % 32 || m > 4096 ||
-      n > 4096 || k > 8192) {
-    g_last_error = "invalid arguments (M, N multiples of 16 up to 4096; K a multiple of 32 up to 8192)";
-    return 1;
-  }
-  HIP_TRY(hipSetDevice(device));
-  const size_t a_bytes = static_cast<size_t>(m) * k * 2, b_bytes = static_cast<size_t>(k) * n * 2;
-  return gemm_on_host_operands({{a_bf16, a_bytes}, {b_bf16, b_bytes}}, c, static_cast<size_t>(m) * n,
-                               [&](const void* const* d, float* dc) {
-                                 hipLaunchKernelGGL(mfma_gemm, dim3(n / 16, m / 16), dim3(64), 0, nullptr,
-                                                    static_cast<const __bf16*>(d[0]), static_cast<const __bf16*>(d[1]), dc, m, n, k);
-                               });
+  return gemm_run<Bf16Path>(device, m, n, k, a_bf16, b_bf16, c,
+                            "invalid arguments (M, N multiples of 16 up to 4096; K a multiple of 32 up to 8192)");
 }
 
 int bgc_diag_mx_gemm(int device, int fmt, int m, int n, int k, const uint8_t* a, const uint8_t* a_scales,

@@ -107,6 +107,20 @@ std::string planted(const char* what, Fn entry, A... args) {
   return dump_nogil([&] { return bgc::gpu::Diag::instance().call(what, entry, args...); });
 }
 
+using AccPlant = std::tuple<int, int, int, int, float>;       // check: wave, round, lane, i, delta; rate: wave, lane, chain, i, delta
+using LowpPlant = std::tuple<int, int, int, int, int, float>;  // the variant or path (check), or the format or path (rate), in front
+
+// The MX or the classic planted entry on its plant tuples as the C structs.
+template <class Fn>
+std::string lowp_planted(const char* what, Fn entry, int device, int waves_per_cu, int iters, unsigned seed,
+                         const std::vector<LowpPlant>& check, const std::vector<LowpPlant>& rate) {
+  std::vector<bgc_lowp_check_plant> c;
+  std::vector<bgc_lowp_rate_plant> r;
+  for (const auto& [variant, wave, round, lane, i, delta] : check) c.push_back({variant, {wave, round, lane, i, delta}});
+  for (const auto& [fmt, wave, lane, chain, i, delta] : rate) r.push_back({fmt, {wave, lane, chain, i, delta}});
+  return planted(what, entry, device, waves_per_cu, iters, seed, c.data(), count(c), r.data(), count(r));
+}
+
 // A walk's result plus "chunk_list": [[device address, bytes], ...]
 Value with_chunk_list(Value v, const std::vector<bgc_walk_chunk>& chunks) {
   Value list = Value::array();
@@ -324,8 +338,6 @@ void register_gpu(py::module_& m) {
     for (const auto& [word, mask] : plants) p.push_back({word, mask});
     return planted("pcie diag", BGC_DIAG_ENTRY(bgc_diag_pcie_planted), device, bytes, seed, p.data(), count(p));
   }, py::arg("device"), py::arg("bytes"), py::arg("seed"), py::arg("plants"));
-  using AccPlant = std::tuple<int, int, int, int, float>;       // check: wave, round, lane, i, delta; rate: wave, lane, chain, i, delta
-  using LowpPlant = std::tuple<int, int, int, int, int, float>;  // the variant (check) or format (rate) in front
   m.def("diag_mfma_planted", [](int device, int waves_per_cu, int iters, unsigned seed, const std::vector<AccPlant>& check,
                                 const std::vector<AccPlant>& rate) {
     std::vector<bgc_mfma_check_plant> c;
@@ -338,22 +350,12 @@ void register_gpu(py::module_& m) {
      py::arg("rate_plants"));
   m.def("diag_mfma_lowp_planted", [](int device, int waves_per_cu, int iters, unsigned seed, const std::vector<LowpPlant>& check,
                                      const std::vector<LowpPlant>& rate) {
-    std::vector<bgc_lowp_check_plant> c;
-    std::vector<bgc_lowp_rate_plant> r;
-    for (const auto& [variant, wave, round, lane, i, delta] : check) c.push_back({variant, {wave, round, lane, i, delta}});
-    for (const auto& [fmt, wave, lane, chain, i, delta] : rate) r.push_back({fmt, {wave, lane, chain, i, delta}});
-    return planted("low-precision mfma diag", BGC_DIAG_ENTRY(bgc_diag_mfma_lowp_planted), device, waves_per_cu, iters, seed,
-                   c.data(), count(c), r.data(), count(r));
+    return lowp_planted("low-precision mfma diag", BGC_DIAG_ENTRY(bgc_diag_mfma_lowp_planted), device, waves_per_cu, iters, seed, check, rate);
   }, py::arg("device"), py::arg("waves_per_cu"), py::arg("iters"), py::arg("seed"), py::arg("check_plants"),
      py::arg("rate_plants"));
   m.def("diag_mfma_classic_planted", [](int device, int waves_per_cu, int iters, unsigned seed, const std::vector<LowpPlant>& check,
                                         const std::vector<LowpPlant>& rate) {
-    std::vector<bgc_lowp_check_plant> c;
-    std::vector<bgc_lowp_rate_plant> r;
-    for (const auto& [path, wave, round, lane, i, delta] : check) c.push_back({path, {wave, round, lane, i, delta}});
-    for (const auto& [path, wave, lane, chain, i, delta] : rate) r.push_back({path, {wave, lane, chain, i, delta}});
-    return planted("classic mfma diag", BGC_DIAG_ENTRY(bgc_diag_mfma_classic_planted), device, waves_per_cu, iters, seed,
-                   c.data(), count(c), r.data(), count(r));
+    return lowp_planted("classic mfma diag", BGC_DIAG_ENTRY(bgc_diag_mfma_classic_planted), device, waves_per_cu, iters, seed, check, rate);
   }, py::arg("device"), py::arg("waves_per_cu"), py::arg("iters"), py::arg("seed"), py::arg("check_plants"),
      py::arg("rate_plants"));
   m.def("diag_lds_planted", [](int device, int wgs_per_cu, int rate_iters, unsigned seed,

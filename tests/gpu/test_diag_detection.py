@@ -313,6 +313,48 @@ def test_mfma_lowp_plant_in_every_wave_of_two_variants():
     _check_cu_keys(r)
 
 
+def test_mfma_lowp_one_plant_in_each_variant_lands_in_its_own_bin():
+    """All four check launches of one run at once: each variant's plant, at a place of its own, reaches
+    that variant's counter and no other."""
+    from bacchus_gpu_controller_amd import ops
+
+    places = [(0, 0, 0, 0), (WAVES - 1, LOWP_ROUNDS - 1, 63, 3), (5, 1, 17, 2), (WAVES // 2, 0, 46, 1)]
+    plants = [(v,) + at + (1.0,) for v, at in zip(LOWP_VARIANTS, places)]
+    r = ops.mfma_lowp_planted(plants, waves_per_cu=WPC, iters=RATE_ITERS)
+    for v in LOWP_VARIANTS:
+        assert r[v + "_mismatches"] == 1, (v, r)
+    assert r["mismatches"] == 4, r
+    assert r["tiles_checked"] == 4 * (WAVES // 4) * 4 * LOWP_ROUNDS, r  # variants x blocks x waves of a block x rounds
+    assert r["throughput_ok"] is True and r["passed"] is False, r
+    _check_cu_keys(r)
+
+
+# what a run reports besides its rates and times
+_MFMA_COUNTS = ["tiles_checked", "cus_seen", "bad_cus", "xccs_seen", "mismatches", "throughput_ok"]
+_LOWP_COUNTS = ["tiles_checked", "cus_seen", "bad_cus", "mismatches", "throughput_ok"] + [v + "_mismatches" for v in LOWP_VARIANTS]
+
+
+def test_mfma_planted_without_plants_is_the_production_run():
+    from bacchus_gpu_controller_amd import ops
+
+    clean = ops.mfma(waves_per_cu=WPC, iters=RATE_ITERS)
+    r = ops.mfma_planted([], [], waves_per_cu=WPC, iters=RATE_ITERS)
+    assert list(r) == list(clean), (r, clean)
+    assert {k: r[k] for k in _MFMA_COUNTS} == {k: clean[k] for k in _MFMA_COUNTS}, (r, clean)
+    assert sum(r["xcc_waves"]) == sum(clean["xcc_waves"]) == WAVES, (r, clean)
+    assert r["bad_cu_keys"] == clean["bad_cu_keys"] == [] and r["passed"] is clean["passed"] is True, (r, clean)
+
+
+def test_mfma_lowp_planted_without_plants_is_the_production_run():
+    from bacchus_gpu_controller_amd import ops
+
+    clean = ops.mfma_lowp(waves_per_cu=WPC, iters=RATE_ITERS)
+    r = ops.mfma_lowp_planted([], [], waves_per_cu=WPC, iters=RATE_ITERS)
+    assert list(r) == list(clean), (r, clean)
+    assert {k: r[k] for k in _LOWP_COUNTS} == {k: clean[k] for k in _LOWP_COUNTS}, (r, clean)
+    assert r["bad_cu_keys"] == clean["bad_cu_keys"] == [] and r["passed"] is clean["passed"] is True, (r, clean)
+
+
 @pytest.mark.parametrize("fmt", ["fp8", "fp4"])
 def test_mfma_lowp_rate_phase_plant_clears_throughput_ok(fmt):
     from bacchus_gpu_controller_amd import ops

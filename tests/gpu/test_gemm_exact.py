@@ -46,7 +46,7 @@ SEED = 0x5EED
 # ---------------------------------------------------------------------------------------------
 # bf16 kernels
 
-KERNEL_NAMES = {"mfma": "mfma_gemm", "soak128": "gemm_soak<128,128,2,2>", "soak256": "gemm_soak<256,256,2,4>",
+KERNEL_NAMES = {"mfma": "dense_gemm<Bf16Path, float>", "soak128": "gemm_soak<128,128,2,2>", "soak256": "gemm_soak<256,256,2,4>",
                 "pingpong": "gemm_pingpong"}
 # environment that forces the kernel for any shape it can run, and what diag_gemm_soak then reports
 _FORCE = {"soak128": ({"BGC_SOAK_TILE": "128"}, (128, "2buf")), "soak256": ({"BGC_SOAK_KERNEL": "2buf"}, (256, "2buf")),
