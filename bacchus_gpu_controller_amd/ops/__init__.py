@@ -28,7 +28,7 @@ These are the only compute kernels in the framework: the reference controller ha
 * ``pcie(device)``      — host<->device copy bandwidth, pinned
 * ``device_bdf(device)``— the HIP device's PCI address, to match it to amdsmi / kubelet
 * ``hbm_planted``, ``hbm_walk_planted``, ``pcie_planted``, ``mfma_planted``,
-  ``mfma_lowp_planted``, ``mfma_classic_planted``, ``lds_planted``, ``gemm_soak_planted`` — for tests: the same diagnostics with wrong
+  ``mfma_lowp_planted``, ``mfma_classic_planted``, ``lds_planted``, ``gemm_soak_planted``, ``burn_planted`` — for tests: the same diagnostics with wrong
   values planted in their own data, to show that they are detected (see below)
 * ``mfma_delayed``, ``burn_delayed`` — for tests: the matrix-core throughput and the burn with
   chosen waves or launches made slow by a known time, to show that it reaches the rates
@@ -197,6 +197,14 @@ def burn_delayed(duration_ms, first_delayed_launch, ticks, dtype="bf16", device=
     """The burn's loop (without the telemetry that ``diag_burn`` adds) with every wave of launch
     `first_delayed_launch` (0-based) and of every later one delayed by `ticks`."""
     return json.loads(native().diag_burn_delayed(device, duration_ms, waves_per_cu, seed, dtype, first_delayed_launch, ticks))
+
+
+def burn_planted(duration_ms, plants, dtype="bf16", device=0, waves_per_cu=32, seed=0x5EED):
+    """The burn's loop with `plants` = [(launch, wave, lane, chain, i, delta), ...]: launch `launch`
+    (0-based) adds delta to acc[chain][i] of that lane after its loop and before its comparison.  The
+    first launch runs 2048 iterations, the later ones the retuned length; a launch the burn never
+    reaches has no effect."""
+    return json.loads(native().diag_burn_planted(device, duration_ms, waves_per_cu, seed, dtype, list(plants)))
 
 
 def gemm_soak_planted(m, n, k, launches, plants, device=0, seed=0x5EED):

@@ -171,6 +171,12 @@ typedef struct {
 
 // Sustained MFMA load for `duration_ms` (back-to-back throughput kernels of ~10 ms each):
 // the node agent samples power, clocks, temperatures and throttle residency meanwhile.
+// The first launch runs 2048 iterations; the later ones run the count that its time puts at ~10 ms,
+// at least 64 and at most the largest with K * iters <= 2^23 (2^18 for bf16, K = 32; 2^16 for the MX
+// tiles, K = 128).  The throughput kernel compares acc == iters * tile + c (c <= 3) in fp32, and a
+// tile element is at most K in magnitude, so up to that count every value on either side is an
+// integer below 2^24 and the comparison is exact; bgc_diag_mfma and bgc_diag_mfma_lowp take at most
+// the same counts.
 int bgc_diag_burn(int device, int duration_ms, int waves_per_cu, uint32_t seed, bgc_burn_result* out);
 // The same load on another matrix-core path: BGC_BURN_FP8 / BGC_BURN_FP4 run the MX
 // block-scaled v_mfma_scale_f32_16x16x128_f8f6f4 rate kernel (rates in that dtype's FLOP/s).
@@ -383,6 +389,17 @@ int bgc_diag_mfma_delayed(int device, int waves_per_cu, int throughput_iters, ui
 // the plant point and not from the kernel's start.
 int bgc_diag_burn_delayed(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype,
                           int first_delayed_launch, uint32_t ticks, bgc_burn_result* out);
+// bgc_diag_burn_dtype with value plants: launch `launch` (0-based) of the burn applies the plants that
+// name it, after its loop and before its comparison; every other launch is the production kernel.  So
+// each plant that changes a value adds one to `mismatches`, whichever launch it is in, and nothing
+// else of the result moves.  A `launch` the burn never reaches has no effect; `launch` < 0 is refused
+// with "invalid arguments" before the device is touched.
+typedef struct {
+  int launch;
+  bgc_mfma_rate_plant at;
+} bgc_burn_plant;
+int bgc_diag_burn_planted(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype,
+                          const bgc_burn_plant* plants, int n, bgc_burn_result* out);
 
 // C[row][col] += delta after launch `launch` and before its checksums.  Only the first and the
 // last launch are verified: a plant on any other launch is invalid.

@@ -28,6 +28,8 @@
 //    lane held, for the tests of the generated tiles.
 //  * bgc_diag_mfma_delayed and bgc_diag_burn_delayed make chosen waves of a throughput launch wait on
 //    the constant clock (delay()), for the tests of the rates and times.
+//  * bgc_diag_burn_planted applies value plants in chosen launches of the burn, for the tests of its
+//    mismatch count.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -848,12 +850,52 @@ int classic_run(int device, int waves_per_cu, int throughput_iters, uint32_t see
   return 0;
 }
 
-// bgc_diag_burn_dtype, and bgc_diag_burn_delayed with every wave of the launches from `first_delayed_launch`
-// on delayed by `ticks` (0: no launch is delayed, the production burn)
+// The value plants of a burn (bgc_diag_burn_planted), sorted by the launch they name: a burn has as many
+// launches as its duration allows, so they are one device array and a launch takes its own stretch of it.
+struct BurnValuePlants {
+  std::vector<int> launch;                // ascending
+  std::vector<bgc_mfma_rate_plant> host;  // in the same order
+  DeviceBuffer dev;
+  // Before the device is touched: false unless the list, every plant's launch (>= 0) and its place are valid.
+  bool take(const bgc_burn_plant* plants, int n) {
+    if (!plant_list_ok(plants, n)) return false;
+    std::vector<bgc_burn_plant> sorted(plants, plants + n);
+    std::stable_sort(sorted.begin(), sorted.end(), [](const bgc_burn_plant& a, const bgc_burn_plant& b) { return a.launch < b.launch; });
+    for (const bgc_burn_plant& p : sorted) {
+      if (p.launch < 0 || !rate_plant_ok(p.at)) return false;
+      launch.push_back(p.launch);
+      host.push_back(p.at);
+    }
+    return true;
+  }
+  // Once the launch size is known: refuse a plant in a wave beyond it, then copy the plants to the device.
+  int upload(int blocks) {
+    for (const bgc_mfma_rate_plant& p : host) {
+      if (p.wave >= blocks * (kBlock / 64)) {
+        g_last_error = "invalid arguments: plant in a wave beyond the launch";
+        return 1;
+      }
+    }
+    if (host.empty()) return 0;
+    HIP_TRY(dev.alloc(host.size() * sizeof(bgc_mfma_rate_plant)));
+    HIP_TRY(hipMemcpy(dev.p, host.data(), host.size() * sizeof(bgc_mfma_rate_plant), hipMemcpyHostToDevice));
+    return 0;
+  }
+  RatePlants of(int l) const {
+    const auto [lo, hi] = std::equal_range(launch.begin(), launch.end(), l);
+    if (lo == hi) return {};
+    return {dev.as<const bgc_mfma_rate_plant>() + (lo - launch.begin()), static_cast<int>(hi - lo)};
+  }
+};
+
+// bgc_diag_burn_dtype; bgc_diag_burn_delayed with every wave of the launches from `first_delayed_launch`
+// on delayed by `ticks` (0: no launch is delayed); and bgc_diag_burn_planted with `plants` applied in the
+// launches they name.  No entry point takes both kinds; without either this is the production burn.
 int burn_run(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype, int first_delayed_launch, uint32_t ticks,
-             bgc_burn_result* out) {
+             const bgc_burn_plant* plants, int n, bgc_burn_result* out) {
+  BurnValuePlants value_plants;
   if (!out || duration_ms <= 0 || duration_ms > 600000 || waves_per_cu <= 0 || waves_per_cu > 64 ||
-      dtype < BGC_BURN_BF16 || dtype > BGC_BURN_FP4) {
+      dtype < BGC_BURN_BF16 || dtype > BGC_BURN_FP4 || !value_plants.take(plants, n)) {
     g_last_error = "invalid arguments";
     return 1;
   }
@@ -865,6 +907,7 @@ int burn_run(int device, int duration_ms, int waves_per_cu, uint32_t seed, int d
     delay_plants.host[0].push_back({BGC_PLANT_ALL_WAVES, ticks});
     if (delay_plants.upload(blocks) != 0) return 1;
   }
+  if (value_plants.upload(blocks) != 0) return 1;
   DeviceBuffer fails;
   XccBins xcc;  // the bf16 kernel writes them; the burn does not read them
   HIP_TRY(fails.alloc(sizeof(unsigned), true));
@@ -875,14 +918,24 @@ int burn_run(int device, int duration_ms, int waves_per_cu, uint32_t seed, int d
   // size one launch to ~10 ms at MI355X rates (iters * 4 MFMA per wave), measured below
   int iters = 2048;
   const double flops_per_iter = with_burn_dtype(dtype, [&](auto tile, auto) { return rate_flops<decltype(tile)>(blocks, 1); });
+  // the longest launch whose accumulators the kernel still compares exactly: kK * iters <= 2^23 (gpu_diag.h)
+  const int max_iters = with_burn_dtype(dtype, [](auto tile, auto) { return (1 << 23) / decltype(tile)::kK; });
   float ms = 0.f;
   HIP_TRY(hipEventRecord(total.a, nullptr));
   double sum_flops = 0;
   while (true) {
     const DelayPlants delays = ticks > 0 && out->launches >= first_delayed_launch ? delay_plants.of(0) : DelayPlants{};
+    const RatePlants values = value_plants.of(out->launches);
     if (timed(ev, &ms, [&] {
           with_burn_dtype(dtype, [&](auto tile, auto timed_per_xcc) {
-            launch_rate<decltype(tile), decltype(timed_per_xcc)::value>(blocks, seed, iters, fails.as<unsigned>(), xcc.t(), xcc.w(), delays);
+            auto launch = [&](auto pl) {
+              launch_rate<decltype(tile), decltype(timed_per_xcc)::value>(blocks, seed, iters, fails.as<unsigned>(), xcc.t(), xcc.w(), pl);
+            };
+            if (values.n > 0) {
+              launch(values);
+            } else {
+              launch(delays);
+            }
           });
         }) != 0) {
       return 1;
@@ -893,7 +946,7 @@ int burn_run(int device, int duration_ms, int waves_per_cu, uint32_t seed, int d
       out->tflops_first = tf;
       out->tflops_min = tf;
       // retune the launch length to ~10 ms now that the rate is known
-      iters = std::max(64, std::min(1 << 18, static_cast<int>(iters * (10.0 / std::max(0.01f, ms)))));
+      iters = std::max(64, std::min(max_iters, static_cast<int>(iters * (10.0 / std::max(0.01f, ms)))));
     } else {
       out->tflops_min = std::min(out->tflops_min, tf);
     }
@@ -1013,7 +1066,7 @@ int bgc_diag_burn(int device, int duration_ms, int waves_per_cu, uint32_t seed, 
 }
 
 int bgc_diag_burn_dtype(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype, bgc_burn_result* out) {
-  return burn_run(device, duration_ms, waves_per_cu, seed, dtype, 0, 0, out);
+  return burn_run(device, duration_ms, waves_per_cu, seed, dtype, 0, 0, nullptr, 0, out);
 }
 
 int bgc_diag_burn_delayed(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype, int first_delayed_launch,
@@ -1022,7 +1075,12 @@ int bgc_diag_burn_delayed(int device, int duration_ms, int waves_per_cu, uint32_
     g_last_error = "invalid arguments";
     return 1;
   }
-  return burn_run(device, duration_ms, waves_per_cu, seed, dtype, first_delayed_launch, ticks, out);
+  return burn_run(device, duration_ms, waves_per_cu, seed, dtype, first_delayed_launch, ticks, nullptr, 0, out);
+}
+
+int bgc_diag_burn_planted(int device, int duration_ms, int waves_per_cu, uint32_t seed, int dtype, const bgc_burn_plant* plants, int n,
+                          bgc_burn_result* out) {
+  return burn_run(device, duration_ms, waves_per_cu, seed, dtype, 0, 0, plants, n, out);
 }
 
 int bgc_diag_gemm(int device, int m, int n, int k, const uint16_t* a_bf16, const uint16_t* b_bf16, float* c) {

@@ -108,7 +108,7 @@ std::string planted(const char* what, Fn entry, A... args) {
 }
 
 using AccPlant = std::tuple<int, int, int, int, float>;       // check: wave, round, lane, i, delta; rate: wave, lane, chain, i, delta
-using LowpPlant = std::tuple<int, int, int, int, int, float>;  // the variant or path (check), or the format or path (rate), in front
+using LowpPlant = std::tuple<int, int, int, int, int, float>;  // the variant or path (check), the format or path (rate) or the burn's launch in front
 
 // The MX or the classic planted entry on its plant tuples as the C structs.
 template <class Fn>
@@ -383,6 +383,19 @@ void register_gpu(py::module_& m) {
     });
   }, py::arg("device"), py::arg("duration_ms"), py::arg("waves_per_cu"), py::arg("seed"), py::arg("dtype"),
      py::arg("first_delayed_launch"), py::arg("ticks"));
+  // The burn with value plants: (launch, wave, lane, chain, i, delta), applied in that launch of the burn.
+  m.def("diag_burn_planted", [](int device, int duration_ms, int waves_per_cu, unsigned seed, const std::string& dtype,
+                                const std::vector<LowpPlant>& plants) {
+    const int code = bgc::gpu::burn_dtype_code(dtype);
+    std::vector<bgc_burn_plant> p;
+    for (const auto& [launch, wave, lane, chain, i, delta] : plants) p.push_back({launch, {wave, lane, chain, i, delta}});
+    return dump_nogil([&] {
+      bgc_burn_result r{};
+      Diag::instance().check("burn", BGC_DIAG_ENTRY(bgc_diag_burn_planted)(device, duration_ms, waves_per_cu, seed, code, p.data(),
+                                                                           count(p), &r));
+      return bgc::gpu::to_json(r, code);
+    });
+  }, py::arg("device"), py::arg("duration_ms"), py::arg("waves_per_cu"), py::arg("seed"), py::arg("dtype"), py::arg("plants"));
   m.def("diag_gemm_soak_planted", [](int device, int mm, int nn, int kk, int launches, unsigned seed,
                                      const std::vector<std::tuple<int, int, int, float>>& plants) {
     std::vector<bgc_soak_plant> p;

@@ -166,9 +166,9 @@ def _wide(path, h):
     return (h >> 6) - (1 << 25)
 
 
-def _reference(path, tile):
+def _reference(path, tile, seed=SEED):
     """A (16 x K), B (K x 16) and C = A B as int64, and the hashes both came from"""
-    ha, hb = _hashes(tile, 0xA, 16, K[path]), _hashes(tile, 0xB, K[path], 16)
+    ha, hb = _hashes(tile, 0xA, 16, K[path], seed), _hashes(tile, 0xB, K[path], 16, seed)
     a, b = _wide(path, ha), _wide(path, hb)
     return a, b, a @ b, ha, hb
 
@@ -205,12 +205,18 @@ def _fragment_bits(path, values):
     return out.view("<u4")
 
 
-@pytest.mark.parametrize("tile", TILES)
-@pytest.mark.parametrize("path", PATHS)
-def test_generated_tile_is_the_documented_one(ops, path, tile):
-    lanes = ops.mfma_classic_tile(path, tile, seed=SEED)
+# device 0's seed, the node agent's seed for device 7, and 0; a case under SEED keeps the name it had
+# before the others were added
+TILE_SEEDS = (SEED, 0x5EF4, 0)
+TILE_CASES = [pytest.param(path, tile, seed, id=f"{path}-{tile}" + ("" if seed == SEED else f"-seed_{seed:#x}"))
+              for seed in TILE_SEEDS for tile in TILES for path in PATHS]
+
+
+@pytest.mark.parametrize("path,tile,seed", TILE_CASES)
+def test_generated_tile_is_the_documented_one(ops, path, tile, seed):
+    lanes = ops.mfma_classic_tile(path, tile, seed=seed)
     assert lanes.shape == (64,)
-    a, b, c, _, _ = _reference(path, tile)
+    a, b, c, _, _ = _reference(path, tile, seed)
     per = {"fp16": 8, "int8": 16, "fp32": 1, "fp64": 1}[path]
     for lane in range(64):
         g, rc = lane >> 4, lane & 15

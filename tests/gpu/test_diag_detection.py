@@ -366,6 +366,58 @@ def test_mfma_lowp_rate_phase_plant_clears_throughput_ok(fmt):
 
 
 # ---------------------------------------------------------------------------------------------
+# The rate phases at the most iterations their entry points take: 2^18 for bf16 (K = 32) and 2^16 for
+# the MX and the classic paths (K up to 128), where K * iters reaches 2^23.  The accumulators then
+# hold integers up to 2^23 + 3, the largest at which the fp32 comparison acc == iters * tile + c is
+# still exact and at which a delta of 1 is still representable, so a clean run must pass and one
+# wrong accumulator must still be seen.  One wave per CU keeps every launch at a few milliseconds.
+
+LIMIT_ITERS = {"mfma": 1 << 18, "lowp": 1 << 16, "classic": 1 << 16}
+CLASSIC_PATHS = ["fp16", "int8", "fp32", "fp64"]
+_FAR_END = (WAVES - 1, 63, 3, 3, 1.0)  # rate plant: the last wave, lane 63, chain 3, element 3
+
+
+def _limit_run(ops, family, planted=None):
+    """the family's run at its limit, with the far-end plant in the rate launch of format or path `planted`"""
+    if family == "mfma":
+        r = ops.mfma_planted([], [_FAR_END] if planted else [], waves_per_cu=WPC, iters=LIMIT_ITERS[family])
+        flops = WAVES * LIMIT_ITERS[family] * 4 * 2 * 16 * 16 * 32
+        rate_ms, counters = [flops / (r["tflops"] * 1e12) * 1e3], ["mismatches"]
+    elif family == "lowp":
+        r = ops.mfma_lowp_planted([], [(planted,) + _FAR_END] if planted else [], waves_per_cu=WPC, iters=LIMIT_ITERS[family])
+        flops = WAVES * LIMIT_ITERS[family] * 4 * 2 * 16 * 16 * 128
+        rate_ms = [flops / (r[f + "_tflops"] * 1e12) * 1e3 for f in ("fp8", "fp4")]
+        counters = ["mismatches"] + [v + "_mismatches" for v in LOWP_VARIANTS]
+    else:
+        r = ops.mfma_classic_planted([], [(planted,) + _FAR_END] if planted else [], waves_per_cu=WPC, iters=LIMIT_ITERS[family])
+        rate_ms, counters = r["rate_ms"], ["mismatches"] + [p + "_mismatches" for p in CLASSIC_PATHS]
+    print("rate phase at its limit:", family, planted or "clean", "iters", LIMIT_ITERS[family], "rate_ms", rate_ms, "elapsed_ms",
+          r["elapsed_ms"])
+    return r, counters
+
+
+@pytest.mark.parametrize("family", list(LIMIT_ITERS))
+def test_rate_phase_at_its_iteration_limit_is_clean(family):
+    from bacchus_gpu_controller_amd import ops
+
+    r, counters = _limit_run(ops, family)
+    assert r["throughput_ok"] is True and r["passed"] is True, r
+    assert [r[k] for k in counters] == [0] * len(counters) and r["bad_cus"] == 0, r
+
+
+LIMIT_PLANTS = [("mfma", "bf16"), ("lowp", "fp8"), ("lowp", "fp4")] + [("classic", p) for p in CLASSIC_PATHS]
+
+
+@pytest.mark.parametrize("family,planted", LIMIT_PLANTS, ids=[f"{f}-{p}" for f, p in LIMIT_PLANTS])
+def test_rate_phase_at_its_iteration_limit_sees_a_delta_of_one(family, planted):
+    from bacchus_gpu_controller_amd import ops
+
+    r, counters = _limit_run(ops, family, planted)
+    assert r["throughput_ok"] is False and r["passed"] is False, r
+    assert [r[k] for k in counters] == [0] * len(counters) and r["bad_cus"] == 0, r
+
+
+# ---------------------------------------------------------------------------------------------
 # GEMM soak
 
 # (m, n, k), BGC_SOAK_TILE, (tile, kernel)

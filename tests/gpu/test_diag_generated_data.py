@@ -312,12 +312,24 @@ TILE_VARIANTS = [("bf16", False), ("fp8", False), ("fp8", True), ("fp4", False),
 TILES = [0, 1, 12345, 2**32 - 1]
 
 
-@pytest.mark.parametrize("tile", TILES)
-@pytest.mark.parametrize("path,scaled", TILE_VARIANTS, ids=[p + ("_scaled" if s else "") for p, s in TILE_VARIANTS])
-def test_tile_operands_scales_and_product(path, scaled, tile):
+# device 0's seed, the node agent's seed for device 7, and 0; a case under SEED keeps the name it had
+# before the others were added
+TILE_SEEDS = (SEED, 0x5EF4, 0)
+
+
+def _seed_id(name, tile, seed):
+    return f"{name}-{tile}" + ("" if seed == SEED else f"-seed_{seed:#x}")
+
+
+PRODUCT_CASES = [pytest.param(path, scaled, tile, seed, id=_seed_id(path + ("_scaled" if scaled else ""), tile, seed))
+                 for seed in TILE_SEEDS for tile in TILES for path, scaled in TILE_VARIANTS]
+
+
+@pytest.mark.parametrize("path,scaled,tile,seed", PRODUCT_CASES)
+def test_tile_operands_scales_and_product(path, scaled, tile, seed):
     from bacchus_gpu_controller_amd import ops
 
-    a, b, ea, eb, acc, expect = decode_tile(path, ops.mfma_tile(path, tile, scaled=scaled, seed=SEED))
+    a, b, ea, eb, acc, expect = decode_tile(path, ops.mfma_tile(path, tile, scaled=scaled, seed=seed))
     for name, x in (("A", a), ("B", b)):
         assert np.isin(x, (-1.0, 0.0, 1.0)).all(), f"{name} holds {np.unique(x)[:8]}"
     assert np.isin(ea, (-1, 0, 1)).all() and np.isin(eb, (-1, 0, 1)).all(), (ea, eb)
@@ -346,23 +358,25 @@ def _generator_index(path, k):
     return 32 * g + 16 * half + t
 
 
-@pytest.mark.parametrize("tile", TILES)
-@pytest.mark.parametrize("path", list(K_OF))
-def test_tile_operands_are_the_documented_hash(path, tile):
+HASH_CASES = [pytest.param(path, tile, seed, id=_seed_id(path, tile, seed)) for seed in TILE_SEEDS for tile in TILES for path in K_OF]
+
+
+@pytest.mark.parametrize("path,tile,seed", HASH_CASES)
+def test_tile_operands_are_the_documented_hash(path, tile, seed):
     from bacchus_gpu_controller_amd import ops
 
     scaled = path != "bf16"
-    a, b, ea, eb, _, _ = decode_tile(path, ops.mfma_tile(path, tile, scaled=scaled, seed=SEED))
+    a, b, ea, eb, _, _ = decode_tile(path, ops.mfma_tile(path, tile, scaled=scaled, seed=seed))
     kk = K_OF[path]
     rc, k = np.meshgrid(np.arange(16), np.arange(kk), indexing="ij")  # [rc][k]
     c = _generator_index(path, k)
-    assert np.array_equal(a, operand_hash(SEED, tile, rc, c, 0xA)), "A"
-    want_b = operand_hash(SEED, tile, k, rc, 0xB) if path == "bf16" else operand_hash(SEED, tile, rc, c, 0xB)
+    assert np.array_equal(a, operand_hash(seed, tile, rc, c, 0xA)), "A"
+    want_b = operand_hash(seed, tile, k, rc, 0xB) if path == "bf16" else operand_hash(seed, tile, rc, c, 0xB)
     assert np.array_equal(b.T, want_b), "B"
     if scaled:
         rc4, blk = np.meshgrid(np.arange(16), np.arange(4), indexing="ij")
-        assert np.array_equal(ea, operand_hash(SEED ^ 0x5CA1E, tile, rc4, blk, 0xA)), "A scale exponents"
-        assert np.array_equal(eb, operand_hash(SEED ^ 0x5CA1E, tile, rc4, blk, 0xB)), "B scale exponents"
+        assert np.array_equal(ea, operand_hash(seed ^ 0x5CA1E, tile, rc4, blk, 0xA)), "A scale exponents"
+        assert np.array_equal(eb, operand_hash(seed ^ 0x5CA1E, tile, rc4, blk, 0xB)), "B scale exponents"
 
 
 @pytest.fixture(scope="module", params=list(K_OF))

@@ -65,6 +65,7 @@ CALLS = {
     "mfma_delayed": (lambda ops: ops.mfma_delayed([]), MFMA),
     # the burn's own keys, without the engine's and the sampler's
     "burn_delayed": (lambda ops: ops.burn_delayed(200, 1 << 30, 1000), {k: BURN[k] for k in list(BURN)[:10]}),
+    "burn_planted": (lambda ops: ops.burn_planted(200, []), {k: BURN[k] for k in list(BURN)[:10]}),
 }
 
 

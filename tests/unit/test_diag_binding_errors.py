@@ -61,6 +61,10 @@ REFUSED = {
     "burn_delayed": (lambda n: n.diag_burn_delayed(0, 300, 32, SEED, "bf16", -3, 500), RuntimeError, "burn: invalid arguments"),
     "burn_delayed_dtype": (lambda n: n.diag_burn_delayed(0, 300, 32, SEED, "int8", 2, 500), RuntimeError,
                            "burn dtype must be bf16, fp8 or fp4, not 'int8'"),
+    "burn_planted": (lambda n: n.diag_burn_planted(0, 300, 32, SEED, "fp8", [(1, 0, 0, 5, 0, 1.0)]), RuntimeError,
+                     "burn: invalid arguments"),
+    "burn_planted_dtype": (lambda n: n.diag_burn_planted(0, 300, 32, SEED, "fp16", [(1, 0, 0, 0, 0, 1.0)]), RuntimeError,
+                           "burn dtype must be bf16, fp8 or fp4, not 'fp16'"),
     "gemm_soak_planted": (lambda n: n.diag_gemm_soak_planted(0, 256, 256, 128, 1, SEED, [(0, 300, 0, 1.0)]), RuntimeError,
                           "gemm soak: invalid arguments: " + SOAK_SHAPE + "; plants inside C, on the first or the last launch"),
     "hbm_data": (lambda n: n.diag_hbm_data(0, 129 * MIB, 1, SEED), RuntimeError, "hbm diag: invalid arguments"),

@@ -105,6 +105,30 @@ def test_burn_delayed_refuses_what_the_burn_refuses(nat, duration_ms, waves_per_
     _refused(nat.diag_burn_delayed, 0, duration_ms, waves_per_cu, SEED, "bf16", 2, 1000)
 
 
+OK_BURN = (0,) + OK_ACC  # (launch, wave, lane, chain, i, delta)
+
+
+@pytest.mark.parametrize("plant", [(-1, 0, 0, 0, 0, 1.0), (0, -1, 0, 0, 0, 1.0), (0, 0, 64, 0, 0, 1.0), (0, 0, -1, 0, 0, 1.0),
+                                   (2, 0, 0, 4, 0, 1.0), (2, 0, 0, -1, 0, 1.0), (1 << 30, 0, 0, 0, 4, 1.0), (0, 0, 0, 0, -1, 1.0)],
+                         ids=["launch_-1", "wave_-1", "lane_64", "lane_-1", "chain_4", "chain_-1", "i_4", "i_-1"])
+@pytest.mark.parametrize("dtype", ["bf16", "fp8", "fp4"])
+def test_burn_plant_out_of_range(nat, dtype, plant):
+    """A burn plant adds to an accumulator register of a named lane of a named launch: its place is
+    checked like a rate plant's, and its launch may be any the burn could reach, but not negative."""
+    _refused(nat.diag_burn_planted, 0, 300, 32, SEED, dtype, [OK_BURN, plant])
+
+
+def test_burn_plant_list_too_long(nat):
+    _refused(nat.diag_burn_planted, 0, 300, 32, SEED, "bf16", [OK_BURN] * 4097)  # BGC_DIAG_MAX_PLANTS is 4096
+
+
+@pytest.mark.parametrize("duration_ms,waves_per_cu", [(0, 32), (600001, 32), (300, 0), (300, 65)],
+                         ids=["duration_0", "duration_over_10_min", "waves_0", "waves_65"])
+@pytest.mark.parametrize("plants", [[], [OK_BURN]], ids=["no_plants", "one_plant"])
+def test_burn_planted_refuses_what_the_burn_refuses(nat, plants, duration_ms, waves_per_cu):
+    _refused(nat.diag_burn_planted, 0, duration_ms, waves_per_cu, SEED, "bf16", plants)
+
+
 def test_generated_data_beyond_the_download_cap(nat):
     """The generated-data variants (tests/gpu/test_diag_generated_data.py) copy what a diagnostic
     generated back to the host: at most 128 MiB per call."""
@@ -190,6 +214,12 @@ def test_negative_plant_count():
         (lib.bgc_diag_mfma_delayed, [i32(0), i32(1), i32(64), u32(SEED), None, i32(0), None]),  # no result struct
         (lib.bgc_diag_burn_delayed, [i32(0), i32(300), i32(32), u32(SEED), i32(0), i32(2), u32(1000), None]),
         (lib.bgc_diag_burn_delayed, [i32(0), i32(300), i32(32), u32(SEED), i32(3), i32(2), u32(1000), out]),  # no such dtype
+        (lib.bgc_diag_burn_planted, [i32(0), i32(300), i32(32), u32(SEED), i32(0), plants, i32(-1), out]),
+        (lib.bgc_diag_burn_planted, [i32(0), i32(300), i32(32), u32(SEED), i32(0), None, i32(1), out]),  # a count without a list
+        (lib.bgc_diag_burn_planted, [i32(0), i32(300), i32(32), u32(SEED), i32(0), plants, i32(4097), out]),
+        (lib.bgc_diag_burn_planted, [i32(0), i32(300), i32(32), u32(SEED), i32(0), None, i32(0), None]),  # no result struct
+        (lib.bgc_diag_burn_planted, [i32(0), i32(300), i32(32), u32(SEED), i32(3), None, i32(0), out]),  # no such dtype
+        (lib.bgc_diag_burn_planted, [i32(0), i32(300), i32(32), u32(SEED), i32(-1), plants, i32(1), out]),
     ]
     for fn, args in calls:
         fn.restype = ctypes.c_int
