@@ -14,65 +14,76 @@
 
 namespace bgc::gpu {
 
-// Performance floors that turn the diagnostics into a health gate: a GPU whose HBM or
-// matrix cores run well below what an MI355X delivers is not advertised, even when every
-// pattern and tile checks out.  Defaults sit ~25 % under the rates measured on MI355X at
-// the node agent's default sizes (profiles/archive/diag_floors_r2.json); 0 disables a floor.
-struct DiagFloors {
-  double min_read_gbps = 0;
-  double min_copy_gbps = 0;
-  double min_write_gbps = 0;
-  double min_mfma_tflops = 0;
-  double min_xcc_balance = 0;  // slowest XCC mean wave time / fastest, inverted (0..1]
-  // MX block-scaled low-precision matrix cores (`lowp` section): any wrong tile fails;
-  // rate floors for the dense fp8 and fp4 phases.
-  double min_fp8_tflops = 0;
-  double min_fp4_tflops = 0;
-  int min_xccs = 0;            // XCCs that must have run MFMA work
-  // fp16 / int8 / fp32 / fp64 matrix-core paths (`classic` section): any wrong tile element fails;
-  // rate floors on each path's dense MFMA rate (int8 in TOP/s).
-  double min_fp16_tflops = 0;
-  double min_int8_tops = 0;
-  double min_fp32_tflops = 0;
-  double min_fp64_tflops = 0;
-  // Local Data Share (`lds` section): any word of the per-CU march that reads back wrong fails; rate
-  // floor on the aggregate LDS read rate, and the share of the device's CUs (cus_seen / cus) that a
-  // march workgroup must have run on.
-  double min_lds_read_tbps = 0;
-  double min_lds_cu_coverage = 0;
-  // Burn-in (sustained MFMA load, `burn` section): rate floor, the rate may not sag
-  // below this fraction of its first launch, and the thermal limits under load.
-  double min_burn_tflops = 0;
-  double min_burn_sustain = 0;   // tflops_last / tflops_max
-  double max_burn_hotspot_c = 0;
-  double max_burn_thermal_violation_pct = 0;
-  // PCIe (`pcie` section): host<->device DMA rates, and the link must run at its full
-  // width (and at least this fraction of its top speed) while the copies run.
-  double min_pcie_h2d_gbps = 0;
-  double min_pcie_d2h_gbps = 0;
-  bool require_full_pcie_width = false;
-  double min_pcie_speed_fraction = 0;
-  // GEMM soak (`soak` section): every checksum must match; rate floor on the mean.
-  double min_soak_tflops = 0;
-  // HBM walk (`hbm_walk` section): any mismatch fails; the walk must cover at least this
-  // share of the free VRAM (a failed allocation on an idle, fenced GPU means something
-  // else holds its memory).
-  double min_hbm_walk_coverage = 0;
-  // Node-level burn (diag_runner.h): under the shared load every GPU must reach this
-  // fraction of the node's fastest GPU, and the summed draw must stay under the limit.
-  double min_node_burn_balance = 0;
-  double max_node_power_w = 0;
-  static DiagFloors mi355x_defaults();
+// read(name, field&) for every (name, member pointer) of `fields`: a struct read or written by its fields' names.
+template <class T, class Fields, class Read>
+void apply_fields(T& object, const Fields& fields, Read&& read) {
+  for (const auto& f : fields) std::visit([&](auto member) { read(f.first, object.*member); }, f.second);
+}
 
-  // Every field above by its name: the one list behind the node agent's CONF_DIAG_<FIELD> and
-  // judge_diag's floors JSON.  A floor missing from it is not configurable.
+// Performance floors that turn the diagnostics into a health gate: a GPU whose HBM or matrix cores run well below what
+// an MI355X delivers is not advertised, even when every pattern and tile checks out.  Each member starts at its MI355X
+// default, ~25 % under the rate measured at the node agent's default sizes; 0 (false) disables a floor.
+struct DiagFloors {
+  // `hbm` and `mfma` sections.  MI355X, ROCm 7.2, 1 GiB buffers / 16 waves per CU x 2048 MFMA iterations
+  // (profiles/archive/diag_floors_r2.json): read 6.33-6.57 TB/s, copy 5.36-5.42, write 5.11-5.25, MFMA bf16 1.92-2.06 PF/s,
+  // XCC balance 0.96.  At 256 MiB (Infinity-Cache-sized, the smallest sensible buffer) read is still 5.56 TB/s, so these
+  // floors hold down to it.
+  double min_read_gbps = 4750, min_copy_gbps = 4000, min_write_gbps = 3800;
+  double min_mfma_tflops = 1500;
+  double min_xcc_balance = 0.85;  // slowest XCC mean wave time / fastest, inverted (0..1]
+  // MX block-scaled low-precision matrix cores (`lowp` section): any wrong tile fails; rate floors for the dense fp8 and
+  // fp4 phases.  v_mfma_scale_f32_16x16x128_f8f6f4, 32 waves per CU x 4096 iterations (profiles/mx_lowp_r3/): 4.1-4.7 PF/s
+  // fp8 and 7.3-8.1 PF/s fp4 depending on how warm the clocks are, against ~5 and ~10 PF/s dense peaks
+  double min_fp8_tflops = 3000, min_fp4_tflops = 5000;
+  int min_xccs = 8;  // XCCs that must have run MFMA work
+  // fp16 / int8 / fp32 / fp64 matrix-core paths (`classic` section): any wrong tile element fails; rate floors on each
+  // path's dense MFMA rate (int8 in TOP/s).  32 waves per CU x 8192 iterations, right after the MX check
+  // (profiles/mfma_classic/rates.json): over 12 runs back to back fp16 2177-2288 TF/s, int8 4204-4424 TOP/s, fp32
+  // 155.8-157.5 and fp64 78.0-78.3 TF/s; in whole passes in a fresh process 2074-2090, 3902-3979, 146.4-148.2 and
+  // 77.2-77.7.  Each floor is 25 % under the lowest run of its path.
+  double min_fp16_tflops = 1550, min_int8_tops = 2900, min_fp32_tflops = 109, min_fp64_tflops = 57;
+  // Local Data Share (`lds` section): any word of the per-CU march that reads back wrong fails; rate floor on the aggregate
+  // LDS read rate, and the share of the device's CUs (cus_seen / cus) that a march workgroup must have run on.  4 march
+  // workgroups per CU, then 8192 sweeps of 512-thread 16-byte reads, right after the MFMA check
+  // (profiles/lds_diag/lds_rate.json): 121-138 TB/s over 12 runs back to back, rising as the clocks warm, and 116-120 TB/s
+  // in whole passes in a fresh worker process, against ~150 TB/s at 2.4 GHz; the march reached 256 of 256 CUs in every run
+  double min_lds_read_tbps = 85;
+  double min_lds_cu_coverage = 1.0;
+  // Burn-in (sustained MFMA load, `burn` section): rate floor, the rate may not sag below this fraction of its best launch,
+  // and the thermal limits under load.  Measured on MI355X in profiles/archive/diag_burn_r2.json (sustained bf16 MFMA at
+  // 97 % of the 2.5 PF/s dense peak once clocks settle)
+  double min_burn_tflops = 1800;  // measured 2409-2421 PF/s mean over 10 s at 1.17-1.22 kW, 2.34-2.39 GHz
+  double min_burn_sustain = 0.80;  // tflops_last / tflops_max
+  double max_burn_hotspot_c = 100;
+  double max_burn_thermal_violation_pct = 20;
+  // PCIe (`pcie` section): host<->device DMA rates, and the link must run at its full width (and at least this fraction of
+  // its top speed) while the copies run.  Gen5 x16 host link (profiles/archive/pcie_r2/probe.json): 57.1 GB/s
+  // host-to-device and 56.7 GB/s device-to-host with 64 MiB - 1 GiB pinned copies, 97 GB/s both ways at once; a
+  // Gen4-trained or x8 link delivers half of that.
+  double min_pcie_h2d_gbps = 45, min_pcie_d2h_gbps = 45;
+  bool require_full_pcie_width = true;
+  double min_pcie_speed_fraction = 0.5;
+  // GEMM soak (`soak` section): every checksum must match; rate floor on the mean.  8-phase ping-pong bf16 MFMA, 256x256
+  // tiles: 1463-1587 TF/s at 8192^3 and 1348-1444 at 4096^3 on MI355X (profiles/gemm_soak_r3/); the floor stays where
+  // round 2's double-buffered kernel (1253-1361 TF/s) also passes, for BGC_SOAK_KERNEL=2buf
+  double min_soak_tflops = 950;
+  // HBM walk (`hbm_walk` section): any mismatch fails; the walk must cover at least this share of the free VRAM (a failed
+  // allocation on an idle, fenced GPU means something else holds its memory).  0.9 of free VRAM is requested; 0.8 leaves
+  // room for allocator granularity
+  double min_hbm_walk_coverage = 0.8;
+  // Node-level burn (judge_node_burn, diag_runner.h): under the shared load every GPU must reach this fraction of the
+  // node's fastest GPU, and the summed draw must stay under the limit.  One GPU 15 % behind the node's fastest is a cooling
+  // or power-delivery outlier (healthy MI355X burns agree within ~1 %, profiles/archive/diag_burn_r2.json); the node power
+  // limit is site-specific (0 = off)
+  double min_node_burn_balance = 0.85;
+  double max_node_power_w = 0;
+  static DiagFloors mi355x_defaults() { return DiagFloors(); }
+  // Every member by its name (a static_assert in diag.cc holds the list to that): what the node agent reads as
+  // CONF_DIAG_<FIELD> and judge_diag as its floors JSON.
   using Field = std::variant<double DiagFloors::*, bool DiagFloors::*, int DiagFloors::*>;
   static const std::vector<std::pair<std::string, Field>>& fields();
-  // read(name, field) for every field, the field as double&, bool& or int&.
   template <class Read>
-  void apply(Read&& read) {
-    for (const auto& f : fields()) std::visit([&](auto member) { read(f.first, this->*member); }, f.second);
-  }
+  void apply(Read&& read) { apply_fields(*this, fields(), read); }  // the field as double&, bool& or int&
 };
 
 // Burn dtype names ("bf16", "fp8", "fp4") <-> BGC_BURN_*; the name throws on anything else.
@@ -81,10 +92,6 @@ const char* burn_dtype_name(int code);
 // Dense-rate ratio of a burn dtype to bf16 on MI355X, as the burn kernels measure it (fp8
 // 2.0x, fp4 3.5x; profiles/mx_lowp_r3/): the bf16 burn floor scales by it.
 double burn_dtype_rate_ratio(int code);
-
-// Pure verdict over one GPU's results ({"hbm":…, "mfma":…, "gemm":…}): adds "passed" and
-// "failures" (one string per violated check) to a copy of `result`.
-json::Value judge_diag(const json::Value& result, const DiagFloors& floors);
 
 // The result structs as JSON: one shape for a diagnostic and its planted variant.
 json::Value to_json(int device, const bgc_hbm_result& r);

@@ -11,9 +11,7 @@
 #include <mutex>
 #include <thread>
 
-#include <fcntl.h>
 #include <signal.h>
-#include <sys/file.h>
 #include <sys/prctl.h>
 #include <unistd.h>
 
@@ -71,34 +69,27 @@ void sleep_until(std::chrono::steady_clock::time_point t) {
   if (t > std::chrono::steady_clock::now()) std::this_thread::sleep_until(t);
 }
 
-// flock(2) on a file: PCIe sections of concurrent worker processes take turns.
-class FileLock {
+// A side thread that calls sample(done) again and again until stop(), which joins it; the destructor stops
+// it too, so it never outlives an exception in the work it samples.  Read what it gathered after stop().
+class Sampler {
  public:
-  explicit FileLock(const std::string& path) {
-    if (path.empty()) return;
-    fd_ = ::open(path.c_str(), O_RDWR | O_CREAT | O_CLOEXEC, 0600);
-    if (fd_ >= 0) {
-      while (::flock(fd_, LOCK_EX) != 0 && errno == EINTR) {
-      }
-    }
+  template <class Sample>
+  explicit Sampler(Sample sample) : thread_([this, sample] { while (!done_.load()) sample(done_); }) {}
+  ~Sampler() { stop(); }
+  void stop() {
+    done_ = true;
+    if (thread_.joinable()) thread_.join();
   }
-  ~FileLock() {
-    if (fd_ >= 0) ::close(fd_);  // releases the lock
-  }
-  bool held() const { return fd_ >= 0; }
-  FileLock(const FileLock&) = delete;
-  FileLock& operator=(const FileLock&) = delete;
 
  private:
-  int fd_ = -1;
+  std::atomic<bool> done_{false};
+  std::thread thread_;
 };
 
-// Iterations of each classic path's rate launch: 1.9-2.1 ms fp16, 2.0-2.3 ms int8, 3.5-3.8 ms fp32 and
-// 7.0-7.1 ms fp64 on the MI355X (profiles/mfma_classic/rates.json)
-constexpr int kClassicIters = 8192;
-
-// Sweeps of the LDS rate phase: 2.4-2.9 ms on the MI355X (profiles/lds_diag/lds_rate.json)
-constexpr int kLdsRateIters = 8192;
+std::string lower(std::string s) {
+  for (auto& c : s) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
+  return s;
+}
 
 class HipDiagEngine : public DiagEngine {
  public:
@@ -107,53 +98,17 @@ class HipDiagEngine : public DiagEngine {
   Value checks(Backend& backend, const GpuInfo& g, int dev, const DiagPlan& plan, uint32_t seed) override {
     Diag& d = Diag::instance();
     (void)d.device_arch(dev);  // HIP up: when this happened tells the agent a worker's start-up time
-    Value r = Value::object();
-    r["ready_at_ns"] = static_cast<long long>(
-        std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count());
-    Value timing = Value::object();  // wall ms per section, to see where a pass spends its time
     auto t = std::chrono::steady_clock::now();
-    auto lap = [&](const char* name) {
+    Value r = Value::object();
+    r["ready_at_ns"] = static_cast<long long>(std::chrono::duration_cast<std::chrono::nanoseconds>(t.time_since_epoch()).count());
+    Value timing = Value::object();  // wall ms per section, to see where a pass spends its time
+    const DiagRun run{g, dev, plan, seed, pcie_lock_path_};
+    for (const DiagSection& s : diag_sections()) {
+      if (!s.planned || !s.planned(plan)) continue;
+      r[s.name] = s.run(d, backend, run);
       const auto now = std::chrono::steady_clock::now();
-      timing[name] = std::chrono::duration<double, std::milli>(now - t).count();
+      timing[s.name] = std::chrono::duration<double, std::milli>(now - t).count();
       t = now;
-    };
-    r["hbm"] = d.hbm(dev, plan.hbm_bytes, 2, seed);
-    lap("hbm");
-    if (plan.hbm_walk_fraction > 0) {
-      r["hbm_walk"] = d.hbm_walk(dev, plan.hbm_walk_fraction, plan.hbm_walk_chunk_bytes, plan.hbm_walk_budget_ms, seed);
-      lap("hbm_walk");
-    }
-    r["mfma"] = d.mfma(dev, 16, 2048, seed);
-    lap("mfma");
-    if (plan.lowp) {
-      r["lowp"] = d.mfma_lowp(dev, 32, 4096, seed);  // ~5 ms
-      lap("lowp");
-    }
-    if (plan.classic) {
-      r["classic"] = d.mfma_classic(dev, 32, kClassicIters, seed);
-      lap("classic");
-    }
-    if (plan.lds) {
-      r["lds"] = d.lds(dev, 4, kLdsRateIters, seed);
-      lap("lds");
-    }
-    r["gemm"] = d.gemm_check(dev, 64, 64, 512, seed);
-    lap("gemm");
-    if (plan.pcie_bytes > 0) {
-      // One GPU at a time: eight concurrent pinned-copy streams share the host's memory
-      // bandwidth and root complexes, so concurrent rates would measure the host, not
-      // the GPU's link.  ~50 ms per GPU.
-      static std::mutex pcie_mu;
-      std::lock_guard<std::mutex> lk(pcie_mu);
-      FileLock across_processes(pcie_lock_path_);
-      r["pcie"] = pcie_check(backend, g, dev, plan.pcie_bytes, seed);
-      // false: the lock file could not be opened, so other GPUs' copies may have overlapped
-      if (!pcie_lock_path_.empty()) r["pcie"]["serialized"] = across_processes.held();
-      lap("pcie");
-    }
-    if (plan.soak_launches > 0) {
-      r["soak"] = d.gemm_soak(dev, plan.soak_size, plan.soak_size, plan.soak_size, plan.soak_launches, seed);
-      lap("soak");
     }
     r["timing_ms"] = timing;
     return r;
@@ -265,12 +220,8 @@ class ProcessDiagEngine : public DiagEngine {
     }
   }
 
- public:
-
- private:
   void set_device_bdfs(std::map<int, std::string> bdfs) override { bdfs_ = std::move(bdfs); }
 
- private:
   std::string exe_, kind_, fixture_, lock_;
   std::map<int, std::string> bdfs_;  // ROCr device -> the BDF its worker must find
   const CancelToken* cancel_;
@@ -288,35 +239,9 @@ class ScriptedDiagEngine : public DiagEngine {
     const Value& e = script.get("gpus").get(std::to_string(g.index));
     std::this_thread::sleep_for(std::chrono::milliseconds(static_cast<int64_t>(num(e, "checks_ms", num(script, "checks_ms", 100)))));
     Value r = Value::object();
-    r["hbm"] = Value::object({{"device", dev}, {"bytes", static_cast<unsigned long long>(plan.hbm_bytes)}, {"read_gbps", 6400.0},
-                              {"write_gbps", 5200.0}, {"copy_gbps", 5400.0}, {"mismatches", 0}, {"passed", true}});
-    if (plan.hbm_walk_fraction > 0) {
-      const uint64_t free_b = g.vram_total_mb * (1ULL << 20);
-      const uint64_t covered = static_cast<uint64_t>(static_cast<double>(free_b) * plan.hbm_walk_fraction);
-      const uint64_t bad = static_cast<uint64_t>(num(e, "walk_mismatches", 0));
-      r["hbm_walk"] = Value::object({{"device", dev}, {"free_bytes", static_cast<unsigned long long>(free_b)},
-                                     {"bytes_covered", static_cast<unsigned long long>(covered)},
-                                     {"coverage_of_free", plan.hbm_walk_fraction}, {"passes", 2},
-                                     {"mismatches", static_cast<unsigned long long>(bad)}, {"passed", bad == 0}});
-    }
-    r["mfma"] = Value::object({{"device", dev}, {"tflops", 2000.0}, {"xcc_balance", 0.96}, {"xccs_seen", 8},
-                               {"mismatches", 0}, {"bad_cus", 0}, {"throughput_ok", true}, {"passed", true}});
-    if (plan.lowp) {
-      r["lowp"] = Value::object({{"device", dev}, {"fp8_tflops", 4000.0}, {"fp4_tflops", 7000.0}, {"mismatches", 0},
-                                 {"bad_cus", 0}, {"throughput_ok", true}, {"passed", true}});
-    }
-    if (plan.classic) {
-      r["classic"] = Value::object({{"device", dev}, {"fp16_tflops", 2000.0}, {"int8_tops", 4000.0}, {"fp32_tflops", 150.0},
-                                    {"fp64_tflops", 75.0}, {"mismatches", 0}, {"bad_cus", 0}, {"throughput_ok", true},
-                                    {"passed", true}});
-    }
-    if (plan.lds) {
-      r["lds"] = Value::object({{"device", dev}, {"cus", 256}, {"cus_seen", 256}, {"bad_cus", 0}, {"mismatches", 0},
-                                {"read_tbps", 100.0}, {"rate_ok", true}, {"cu_balance", 0.97}, {"passed", true}});
-    }
-    r["gemm"] = Value::object({{"passed", true}});
-    if (plan.soak_launches > 0) {
-      r["soak"] = Value::object({{"tflops_mean", 1300.0}, {"row_mismatches", 0}, {"col_mismatches", 0}, {"passed", true}});
+    const DiagRun run{g, dev, plan, 0, "", &e};
+    for (const DiagSection& s : diag_sections()) {
+      if (s.planned && s.planned(plan) && s.scripted) r[s.name] = s.scripted(run);
     }
     if (e.get("fail").is_string()) r["error"] = e.get_string("fail");
     return r;
@@ -357,40 +282,6 @@ std::vector<std::string> worker_device_bdfs(const std::string& exe) {
   return out;
 }
 
-Value to_json(const DiagPlan& p) {
-  return Value::object({{"hbm_bytes", static_cast<unsigned long long>(p.hbm_bytes)},
-                        {"hbm_walk_fraction", p.hbm_walk_fraction},
-                        {"hbm_walk_chunk_bytes", static_cast<unsigned long long>(p.hbm_walk_chunk_bytes)},
-                        {"hbm_walk_budget_ms", p.hbm_walk_budget_ms},
-                        {"pcie_bytes", static_cast<unsigned long long>(p.pcie_bytes)},
-                        {"soak_size", p.soak_size},
-                        {"soak_launches", p.soak_launches},
-                        {"lowp", p.lowp},
-                        {"classic", p.classic},
-                        {"lds", p.lds},
-                        {"burn_ms", p.burn_ms},
-                        {"burn_dtype", burn_dtype_name(p.burn_dtype)}});
-}
-
-DiagPlan diag_plan_from_json(const Value& v) {
-  DiagPlan p;
-  auto u64 = [&](const char* k, uint64_t d) { return v.get(k).is_int() ? v.get(k).as_uint() : d; };
-  auto i32 = [&](const char* k, int d) { return v.get(k).is_int() ? static_cast<int>(v.get(k).as_int()) : d; };
-  p.hbm_bytes = u64("hbm_bytes", p.hbm_bytes);
-  p.hbm_walk_fraction = v.get("hbm_walk_fraction").is_number() ? v.get("hbm_walk_fraction").as_double() : p.hbm_walk_fraction;
-  p.hbm_walk_chunk_bytes = u64("hbm_walk_chunk_bytes", p.hbm_walk_chunk_bytes);
-  p.hbm_walk_budget_ms = i32("hbm_walk_budget_ms", p.hbm_walk_budget_ms);
-  p.pcie_bytes = u64("pcie_bytes", p.pcie_bytes);
-  p.soak_size = i32("soak_size", p.soak_size);
-  p.soak_launches = i32("soak_launches", p.soak_launches);
-  p.lowp = v.get("lowp").is_bool() ? v.get("lowp").as_bool() : p.lowp;
-  p.classic = v.get("classic").is_bool() ? v.get("classic").as_bool() : p.classic;
-  p.lds = v.get("lds").is_bool() ? v.get("lds").as_bool() : p.lds;
-  p.burn_ms = i32("burn_ms", p.burn_ms);
-  if (v.get("burn_dtype").is_string()) p.burn_dtype = burn_dtype_code(v.get_string("burn_dtype"));
-  return p;
-}
-
 int diag_worker_main() {
   // The worker must not outlive the agent (a burn or a walk left running on a GPU the
   // restarted agent is about to diagnose): die with the thread that spawned it, which
@@ -422,10 +313,6 @@ int diag_worker_main() {
       // hidden device would put a burn or a verdict on another GPU, maybe a tenant's)
       const std::string expect = op == "checks" ? req.get("gpu").get_string("bdf") : req.get_string("expect_bdf");
       if (!scripted && !expect.empty()) {
-        auto lower = [](std::string v) {
-          for (auto& c : v) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
-          return v;
-        };
         Diag& d = Diag::instance();
         const std::string got = d.device_count() > 0 ? d.device_bdf(dev) : std::string("no device");
         if (lower(got) != lower(expect)) {
@@ -465,28 +352,17 @@ std::unique_ptr<DiagEngine> make_scripted_diag_engine(Backend& backend) {
 
 Value pcie_check(Backend& backend, const GpuInfo& g, int hip_device, uint64_t bytes, uint32_t seed) {
   const Telemetry before = backend.sample(g.index, SampleLevel::Slow);
-  std::atomic<bool> done{false};
   int width = -1, speed = -1;  // highest seen while copying
-  std::thread sampler([&] {
-    while (!done.load()) {
-      Telemetry t = backend.sample(g.index, SampleLevel::Slow);
-      if (t.ok) {
-        width = std::max(width, t.pcie_width);
-        speed = std::max(speed, t.pcie_speed_mts);
-      }
-      for (int i = 0; i < 5 && !done.load(); ++i) std::this_thread::sleep_for(std::chrono::milliseconds(10));
+  Sampler sampler([&](const std::atomic<bool>& done) {
+    Telemetry t = backend.sample(g.index, SampleLevel::Slow);
+    if (t.ok) {
+      width = std::max(width, t.pcie_width);
+      speed = std::max(speed, t.pcie_speed_mts);
     }
+    nap(done, 50);
   });
-  Value out;
-  try {
-    out = Diag::instance().pcie(hip_device, bytes, 5, seed);
-  } catch (...) {
-    done = true;
-    sampler.join();
-    throw;
-  }
-  done = true;
-  sampler.join();
+  Value out = Diag::instance().pcie(hip_device, bytes, 5, seed);
+  sampler.stop();
   const Telemetry after = backend.sample(g.index, SampleLevel::Slow);
   if (width > 0) out["link_width"] = width;
   if (speed > 0) out["link_speed_mts"] = speed;
@@ -506,24 +382,13 @@ Value burn_in(Backend& backend, int index, int hip_device, int duration_ms, uint
     own = make_hip_diag_engine();
     engine = own.get();
   }
-  std::atomic<bool> done{false};
   BurnStats st;
-  std::thread sampler([&] {
-    while (!done.load()) {
-      st.add(backend.sample(index, SampleLevel::Fast));
-      nap(done, 100);
-    }
+  Sampler sampler([&](const std::atomic<bool>& done) {
+    st.add(backend.sample(index, SampleLevel::Fast));
+    nap(done, 100);
   });
-  Value out;
-  try {
-    out = engine->burn(hip_device, duration_ms, seed, dtype, std::chrono::steady_clock::time_point());
-  } catch (...) {
-    done = true;
-    sampler.join();
-    throw;
-  }
-  done = true;
-  sampler.join();
+  Value out = engine->burn(hip_device, duration_ms, seed, dtype, std::chrono::steady_clock::time_point());
+  sampler.stop();
   st.fill(out);
   return out;
 }
@@ -540,7 +405,6 @@ NodeBurnResult node_burn(Backend& backend, DiagEngine& engine, const std::vector
   std::condition_variable cv;
   size_t ready = 0;
   bool go = false;
-  std::atomic<bool> done{false};
   double sum_max = 0, sum_acc = 0, peak_hot = 0;
   int sweeps = 0;
   // Every GPU starts at the same instant: after the engine's start-up lead (a worker
@@ -548,26 +412,24 @@ NodeBurnResult node_burn(Backend& backend, DiagEngine& engine, const std::vector
   const auto start_at = std::chrono::steady_clock::now() + std::chrono::milliseconds(engine.start_lead_ms());
   // One sampler for the whole node: each sweep reads every GPU under load, so the summed
   // power is the node's draw at one moment rather than a sum of separate peaks.
-  std::thread sampler([&] {
-    while (!done.load() && std::chrono::steady_clock::now() < start_at) nap(done, 20);
-    while (!done.load()) {
-      double sum = 0;
-      int ok = 0;
-      for (size_t k = 0; k < n; ++k) {
-        const Telemetry t = backend.sample(gpus[which[k]].index, SampleLevel::Fast);
-        if (!t.ok) continue;
-        st[k].add(t);
-        sum += t.power_w;
-        peak_hot = std::max(peak_hot, t.temp_hotspot_c);
-        ++ok;
-      }
-      if (ok) {
-        sum_max = std::max(sum_max, sum);
-        sum_acc += sum;
-        ++sweeps;
-      }
-      nap(done, 100);
+  Sampler sampler([&](const std::atomic<bool>& done) {
+    if (std::chrono::steady_clock::now() < start_at) return nap(done, 20);
+    double sum = 0;
+    int ok = 0;
+    for (size_t k = 0; k < n; ++k) {
+      const Telemetry t = backend.sample(gpus[which[k]].index, SampleLevel::Fast);
+      if (!t.ok) continue;
+      st[k].add(t);
+      sum += t.power_w;
+      peak_hot = std::max(peak_hot, t.temp_hotspot_c);
+      ++ok;
     }
+    if (ok) {
+      sum_max = std::max(sum_max, sum);
+      sum_acc += sum;
+      ++sweeps;
+    }
+    nap(done, 100);
   });
   std::vector<std::thread> workers;
   const auto t0 = std::chrono::steady_clock::now();
@@ -595,9 +457,7 @@ NodeBurnResult node_burn(Backend& backend, DiagEngine& engine, const std::vector
   for (const auto& r : res.per_gpu) {
     if (r.get("late_ms").is_number()) late_max = std::max(late_max, r.get("late_ms").as_double());
   }
-  done = true;
-  sampler.join();
-  Value per = Value::array();
+  sampler.stop();
   for (size_t k = 0; k < n; ++k) {
     if (!err[k].empty()) {
       res.per_gpu[k] = Value::object({{"error", err[k]}});
@@ -670,10 +530,6 @@ std::vector<std::vector<std::string>> judge_node_burn(NodeBurnResult& r, const D
 }
 
 std::vector<int> hip_devices_for(const std::vector<GpuInfo>& gpus, const std::vector<std::string>& hip_bdfs) {
-  auto lower = [](std::string s) {
-    for (auto& c : s) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
-    return s;
-  };
   std::map<std::string, int> bdf_count, hip_by_bdf;
   for (const auto& g : gpus) bdf_count[lower(g.bdf)]++;
   for (size_t d = 0; d < hip_bdfs.size(); ++d) hip_by_bdf.emplace(lower(hip_bdfs[d]), static_cast<int>(d));

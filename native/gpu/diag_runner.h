@@ -29,23 +29,9 @@
 #include "core/json.h"
 #include "gpu/device.h"
 #include "gpu/diag.h"
+#include "gpu/diag_sections.h"
 
 namespace bgc::gpu {
-
-struct DiagPlan {
-  uint64_t hbm_bytes = 1ULL << 30;       // bandwidth phases (two buffers of this size)
-  double hbm_walk_fraction = 0.9;        // address-pattern walk of this share of free VRAM (0 = off)
-  uint64_t hbm_walk_chunk_bytes = 4ULL << 30;
-  int hbm_walk_budget_ms = 20000;
-  uint64_t pcie_bytes = 256ULL << 20;    // 0 = off
-  int soak_size = 8192;
-  int soak_launches = 20;                // 0 = off
-  bool lowp = true;                      // MX fp8 / fp4 matrix-core tiles and rates
-  bool classic = true;                   // fp16 / int8 / fp32 / fp64 matrix-core tiles and rates
-  bool lds = true;                       // per-CU LDS march and LDS read rate
-  int burn_ms = 0;                       // node-level burn phase (0 = off)
-  int burn_dtype = BGC_BURN_BF16;         // its matrix-core path (bf16, MX fp8, MX fp4)
-};
 
 class DiagEngine {
  public:
@@ -53,7 +39,7 @@ class DiagEngine {
   virtual std::string name() const = 0;
   // How far ahead node_burn schedules a common start (time a burn needs to get ready).
   virtual int start_lead_ms() const { return 0; }
-  // Everything but the burn for one GPU: {"hbm","hbm_walk","mfma","lowp","classic","lds","gemm","pcie","soak"}.
+  // Every section of diag_sections() that the plan runs, for one GPU: all but the burn.
   // Throws on a HIP/library error.
   virtual json::Value checks(Backend& backend, const GpuInfo& g, int hip_device, const DiagPlan& plan,
                              uint32_t seed) = 0;
@@ -84,8 +70,6 @@ std::vector<std::string> worker_device_bdfs(const std::string& exe);
 // "checks" | "burn", ...}), the result JSON (or {"error": ...}) on stdout.
 int diag_worker_main();
 
-json::Value to_json(const DiagPlan& p);
-DiagPlan diag_plan_from_json(const json::Value& v);
 // Replays backend.diag_script() (re-read on every call):
 //   {"checks_ms": 200, "burn_tflops": 2400,
 //    "gpus": {"<index>": {"checks_ms": .., "burn_tflops": .., "walk_mismatches": .., "fail": "<text>"}}}

@@ -9,7 +9,6 @@
 
 #include "core/log.h"
 #include "core/metrics.h"
-#include "gpu/diag.h"
 #include "kube/leader.h"
 #include "kube/runtime.h"
 
@@ -34,11 +33,12 @@ NodeAgentConfig NodeAgentConfig::from_env(const EnvConfig& env) {
   c.label_prefix = env.str_or("label_prefix", "amd.com/gpu");
   c.max_gpus = static_cast<int>(env.u64_or("max_gpus", 0));
   c.run_diag = env.boolean_or("run_diag", false);
-  c.diag_hbm_bytes = env.u64_or("diag_hbm_bytes", 1ULL << 30);
+  DiagPlan& p = c.diag_plan;
+  p.hbm_bytes = env.u64_or("diag_hbm_bytes", p.hbm_bytes);
   c.diag_interval_secs = env.u64_or("diag_interval_secs", 0);
-  c.diag_hbm_walk_fraction = env.f64_or("diag_hbm_walk_fraction", c.diag_hbm_walk_fraction);
-  c.diag_hbm_walk_chunk_mb = env.u64_or("diag_hbm_walk_chunk_mb", c.diag_hbm_walk_chunk_mb);
-  c.diag_hbm_walk_budget_ms = env.u64_or("diag_hbm_walk_budget_ms", c.diag_hbm_walk_budget_ms);
+  p.hbm_walk_fraction = env.f64_or("diag_hbm_walk_fraction", p.hbm_walk_fraction);
+  p.hbm_walk_chunk_bytes = env.u64_or("diag_hbm_walk_chunk_mb", p.hbm_walk_chunk_bytes >> 20) << 20;
+  p.hbm_walk_budget_ms = static_cast<int>(env.u64_or("diag_hbm_walk_budget_ms", static_cast<uint64_t>(p.hbm_walk_budget_ms)));
   c.diag_fence_settle_ms = env.u64_or("diag_fence_settle_ms", c.diag_fence_settle_ms);
   c.diag_start_busy = env.str_or("diag_start_busy", c.diag_start_busy);
   if (c.diag_start_busy != "skip" && c.diag_start_busy != "diagnose") {
@@ -50,15 +50,15 @@ NodeAgentConfig NodeAgentConfig::from_env(const EnvConfig& env) {
     else if constexpr (std::is_same_v<decltype(v), bool&>) v = env.boolean_or(key, v);
     else v = static_cast<int>(env.u64_or(key, static_cast<uint64_t>(v)));
   });
-  c.diag_burn_ms = env.u64_or("diag_burn_ms", 0);
+  p.burn_ms = static_cast<int>(env.u64_or("diag_burn_ms", 0));
   c.diag_burn_dtype = env.str_or("diag_burn_dtype", c.diag_burn_dtype);
   (void)burn_dtype_code(c.diag_burn_dtype);  // bf16 | fp8 | fp4, else the agent does not start
-  c.diag_pcie_bytes = env.u64_or("diag_pcie_bytes", c.diag_pcie_bytes);
-  c.diag_soak_size = static_cast<int>(env.u64_or("diag_soak_size", static_cast<uint64_t>(c.diag_soak_size)));
-  c.diag_soak_launches = static_cast<int>(env.u64_or("diag_soak_launches", static_cast<uint64_t>(c.diag_soak_launches)));
-  c.diag_lowp = env.boolean_or("diag_lowp", c.diag_lowp);
-  c.diag_classic = env.boolean_or("diag_classic", c.diag_classic);
-  c.diag_lds = env.boolean_or("diag_lds", c.diag_lds);
+  p.pcie_bytes = env.u64_or("diag_pcie_bytes", p.pcie_bytes);
+  p.soak_size = static_cast<int>(env.u64_or("diag_soak_size", static_cast<uint64_t>(p.soak_size)));
+  p.soak_launches = static_cast<int>(env.u64_or("diag_soak_launches", static_cast<uint64_t>(p.soak_launches)));
+  p.lowp = env.boolean_or("diag_lowp", p.lowp);
+  p.classic = env.boolean_or("diag_classic", p.classic);
+  p.lds = env.boolean_or("diag_lds", p.lds);
   c.pod_resources_socket = env.str_or("pod_resources_socket", c.pod_resources_socket);
   HealthPolicy& h = c.health;
   h.max_hotspot_c = env.f64_or("max_hotspot_c", h.max_hotspot_c);
@@ -449,22 +449,6 @@ DiagOutcome NodeAgent::diag_outcome() const {
   return diag_;
 }
 
-DiagPlan NodeAgent::diag_plan() const {
-  DiagPlan p;
-  p.hbm_bytes = cfg_.diag_hbm_bytes;
-  p.hbm_walk_fraction = cfg_.diag_hbm_walk_fraction;
-  p.hbm_walk_chunk_bytes = cfg_.diag_hbm_walk_chunk_mb << 20;
-  p.hbm_walk_budget_ms = static_cast<int>(cfg_.diag_hbm_walk_budget_ms);
-  p.pcie_bytes = cfg_.diag_pcie_bytes;
-  p.soak_size = cfg_.diag_soak_size;
-  p.soak_launches = cfg_.diag_soak_launches;
-  p.lowp = cfg_.diag_lowp;
-  p.classic = cfg_.diag_classic;
-  p.lds = cfg_.diag_lds;
-  p.burn_ms = static_cast<int>(cfg_.diag_burn_ms);
-  return p;
-}
-
 void NodeAgent::setup_diag() {
   if (engine_) return;
   const Value script = backend_->diag_script();
@@ -541,34 +525,10 @@ void NodeAgent::record_diag_gauges(size_t i, const Value& r) {
   // per-GPU results as gauges (Prometheus), so fleet dashboards see a slow GPU before it fails a floor
   auto& reg = metrics::Registry::global();
   const metrics::Labels gl{{"gpu", std::to_string(gpus_[i].index)}};
-  struct G {
-    const char *name, *help, *sect, *key;
-  };
-  static const G kGauges[] = {
-      {"amd_gpu_diag_hbm_read_gbps", "Diagnostics: HBM read GB/s", "hbm", "read_gbps"},
-      {"amd_gpu_diag_hbm_write_gbps", "Diagnostics: HBM write GB/s", "hbm", "write_gbps"},
-      {"amd_gpu_diag_hbm_copy_gbps", "Diagnostics: HBM copy GB/s", "hbm", "copy_gbps"},
-      {"amd_gpu_diag_hbm_walk_covered_bytes", "Diagnostics: HBM bytes pattern-walked", "hbm_walk", "bytes_covered"},
-      {"amd_gpu_diag_hbm_walk_mismatches", "Diagnostics: HBM walk words read back wrong", "hbm_walk", "mismatches"},
-      {"amd_gpu_diag_mfma_tflops", "Diagnostics: bf16 MFMA TFLOP/s (register operands)", "mfma", "tflops"},
-      {"amd_gpu_diag_xcc_balance", "Diagnostics: fastest/slowest XCC wave time", "mfma", "xcc_balance"},
-      {"amd_gpu_diag_fp8_tflops", "Diagnostics: MX fp8 MFMA TFLOP/s (register operands)", "lowp", "fp8_tflops"},
-      {"amd_gpu_diag_fp4_tflops", "Diagnostics: MX fp4 MFMA TFLOP/s (register operands)", "lowp", "fp4_tflops"},
-      {"amd_gpu_diag_fp16_tflops", "Diagnostics: fp16 MFMA TFLOP/s (register operands)", "classic", "fp16_tflops"},
-      {"amd_gpu_diag_int8_tops", "Diagnostics: int8 MFMA TOP/s (register operands)", "classic", "int8_tops"},
-      {"amd_gpu_diag_fp32_tflops", "Diagnostics: fp32-input MFMA TFLOP/s (register operands)", "classic", "fp32_tflops"},
-      {"amd_gpu_diag_fp64_tflops", "Diagnostics: fp64 MFMA TFLOP/s (register operands)", "classic", "fp64_tflops"},
-      {"amd_gpu_diag_classic_bad_cus", "Diagnostics: CUs with a wrong fp16 / int8 / fp32 / fp64 MFMA tile element", "classic", "bad_cus"},
-      {"amd_gpu_diag_lds_read_tbps", "Diagnostics: LDS read TB/s, all CUs", "lds", "read_tbps"},
-      {"amd_gpu_diag_lds_bad_cus", "Diagnostics: CUs whose LDS march read back a wrong word", "lds", "bad_cus"},
-      {"amd_gpu_diag_soak_tflops", "Diagnostics: LDS-tiled MFMA GEMM soak TFLOP/s", "soak", "tflops_mean"},
-      {"amd_gpu_diag_pcie_h2d_gbps", "Diagnostics: PCIe host-to-device GB/s", "pcie", "h2d_gbps"},
-      {"amd_gpu_diag_pcie_d2h_gbps", "Diagnostics: PCIe device-to-host GB/s", "pcie", "d2h_gbps"},
-      {"amd_gpu_diag_burn_tflops", "Diagnostics: burn-in mean MFMA TFLOP/s", "burn", "tflops_mean"},
-      {"amd_gpu_diag_burn_max_hotspot_celsius", "Diagnostics: burn-in peak hotspot temperature", "burn", "max_hotspot_c"},
-  };
-  for (const auto& g : kGauges) {
-    if (r.get(g.sect).get(g.key).is_number()) reg.gauge(g.name, g.help, gl).set(get(g.sect, g.key));
+  for (const DiagSection& s : diag_sections()) {
+    for (const DiagNumber& n : s.numbers) {
+      if (n.gauge && r.get(s.name).get(n.key).is_number()) reg.gauge(n.gauge, n.help, gl).set(get(s.name, n.key));
+    }
   }
   reg.gauge("amd_gpu_diag_passed", "1 when the last diagnostics pass of the GPU succeeded", gl)
       .set(r.get("passed").as_bool() ? 1 : 0);
@@ -648,7 +608,7 @@ bool NodeAgent::run_diagnostics(bool at_start) {
     fence_races_ += released.size();
     todo = still;
   }
-  const DiagPlan plan = diag_plan();
+  const DiagPlan& plan = cfg_.diag_plan;
   // Phase 1: every GPU's checks at once, one thread per GPU.
   {
     std::vector<std::thread> threads;
@@ -683,8 +643,8 @@ bool NodeAgent::run_diagnostics(bool at_start) {
   // Phase 2: the node-level burn — every GPU under diagnosis at full MFMA load together.
   Value node = Value();
   std::vector<std::vector<std::string>> node_failures(todo.size());
-  if (cfg_.diag_burn_ms > 0 && !todo.empty()) {
-    NodeBurnResult nb = node_burn(*backend_, *engine_, gpus_, hip_devs_, todo, static_cast<int>(cfg_.diag_burn_ms), 0xb0c4,
+  if (plan.burn_ms > 0 && !todo.empty()) {
+    NodeBurnResult nb = node_burn(*backend_, *engine_, gpus_, hip_devs_, todo, plan.burn_ms, 0xb0c4,
                                   burn_dtype_code(cfg_.diag_burn_dtype));
     node_failures = judge_node_burn(nb, cfg_.diag_floors);
     for (size_t k = 0; k < todo.size(); ++k) results[todo[k]]["burn"] = nb.per_gpu[k];

@@ -75,36 +75,17 @@ struct NodeAgentConfig {
   // "diagnose" runs the start-up pass on them anyway (a fresh node, or a test whose own
   // process holds the GPU)
   std::string diag_start_busy = "skip";
-  uint64_t diag_hbm_bytes = 1ULL << 30;  // bandwidth phases (two buffers)
   uint64_t diag_interval_secs = 0;     // 0 = only at start
-  // Address-pattern walk of this share of each GPU's free VRAM (0 = off), in chunks, with
-  // a time budget after which the second (inverse) pass is skipped.
-  double diag_hbm_walk_fraction = 0.9;
-  uint64_t diag_hbm_walk_chunk_mb = 4096;
-  uint64_t diag_hbm_walk_budget_ms = 20000;
   uint64_t diag_fence_settle_ms = 2000;
-  // Burn-in: sustained MFMA load for this long while power, clocks, temperatures and
-  // throttle residency are sampled (catches cooling/power-delivery faults the short
-  // checks do not); 0 = off.
-  uint64_t diag_burn_ms = 0;
-  // its matrix-core path.  "fp4" (MX block-scaled) drives an MI355X to its power cap:
+  // What a pass runs and how large, each field under CONF_DIAG_<FIELD> but for CONF_DIAG_HBM_WALK_CHUNK_MB.  Its
+  // burn_ms is the node-level burn-in: sustained MFMA load for this long while power, clocks, temperatures and
+  // throttle residency are sampled (catches cooling/power-delivery faults the short checks do not); 0 = off.
+  DiagPlan diag_plan;
+  // The burn's matrix-core path.  "fp4" (MX block-scaled) drives an MI355X to its power cap:
   // 1.30 kW mean, power-limited 71 % of the time, against 1.08-1.17 kW for "bf16" and
   // 1.21 kW for "fp8" (profiles/mx_lowp_r3/burn_dtype.json), so it is the hardest
   // power-delivery and cooling stress.  The bf16 rate floor scales with the dtype.
   std::string diag_burn_dtype = "fp4";
-  // PCIe check: pinned host<->device copies of this size (0 = off) with the link's
-  // width/speed read while they run.
-  uint64_t diag_pcie_bytes = 256ULL << 20;
-  // GEMM soak: `diag_soak_launches` back-to-back LDS-tiled MFMA GEMMs of size^3 (bf16),
-  // checked by exact checksums (0 launches = off).
-  int diag_soak_size = 8192;
-  int diag_soak_launches = 20;
-  // MX block-scaled fp8 / fp4 matrix-core tiles (with and without E8M0 scales) and rates
-  bool diag_lowp = true;
-  // fp16 / int8 / fp32 / fp64 matrix-core tiles with full-width operands, and their rates
-  bool diag_classic = true;
-  // March test of every CU's whole Local Data Share, and the LDS read rate
-  bool diag_lds = true;
   DiagFloors diag_floors = DiagFloors::mi355x_defaults();
   std::string pod_resources_socket = "/var/lib/kubelet/pod-resources/kubelet.sock";
   HealthPolicy health;
@@ -212,7 +193,6 @@ class NodeAgent {
 
  private:
   int healthy_count(std::string* reason) const;
-  DiagPlan diag_plan() const;
   void setup_diag();  // engine + HIP device ids (by BDF); idempotent
   void record_diag_gauges(size_t i, const json::Value& judged);
   std::vector<bool> in_use() const;
