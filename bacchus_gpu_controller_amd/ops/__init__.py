@@ -1,4 +1,4 @@
-"""HIP/CDNA4 GPU health kernels (native/gpu/hip/: hbm.hip, mfma.hip, lds.hip, gemm_soak.hip) exposed to Python.
+"""HIP/CDNA4 GPU health kernels (native/gpu/hip/: hbm.hip, mfma.hip, lds.hip, cache.hip, gemm_soak.hip) exposed to Python.
 
 These are the only compute kernels in the framework: the reference controller has none
 (SURVEY §2.5).  They back the node agent's diagnostics before a GPU is advertised
@@ -14,6 +14,8 @@ These are the only compute kernels in the framework: the reference controller ha
   operands as wide as each path's multipliers
 * ``lds(device)``       — a march test of every CU's whole Local Data Share (160 KiB), attributed to
   the CU, then the aggregate LDS read rate
+* ``cache(device)``     — a march through every XCD's L2 (4 MiB each), attributed to the XCC, and the
+  aggregate L2 read rate; then a pattern check and the read rate of the 256 MiB Infinity Cache
 * ``gemm_check(device)``— a bf16 GEMM on the matrix cores checked element by element against
   a double-precision product of the same operands on the host
 * ``gemm_soak(device)`` — the sustained-throughput soak: the 8-phase ping-pong GEMM
@@ -28,11 +30,11 @@ These are the only compute kernels in the framework: the reference controller ha
 * ``pcie(device)``      — host<->device copy bandwidth, pinned
 * ``device_bdf(device)``— the HIP device's PCI address, to match it to amdsmi / kubelet
 * ``hbm_planted``, ``hbm_walk_planted``, ``pcie_planted``, ``mfma_planted``,
-  ``mfma_lowp_planted``, ``mfma_classic_planted``, ``lds_planted``, ``gemm_soak_planted``, ``burn_planted`` — for tests: the same diagnostics with wrong
+  ``mfma_lowp_planted``, ``mfma_classic_planted``, ``lds_planted``, ``cache_planted``, ``gemm_soak_planted``, ``burn_planted`` — for tests: the same diagnostics with wrong
   values planted in their own data, to show that they are detected (see below)
-* ``mfma_delayed``, ``burn_delayed`` — for tests: the matrix-core throughput and the burn with
-  chosen waves or launches made slow by a known time, to show that it reaches the rates
-* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile``, ``mfma_classic_tile``, ``lds_data`` — for tests:
+* ``mfma_delayed``, ``burn_delayed``, ``cache_delayed`` — for tests: the matrix-core throughput, the burn and the L2 rate with
+  chosen waves, launches or workgroups made slow by a known time, to show that it reaches the rates
+* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile``, ``mfma_classic_tile``, ``lds_data``, ``cache_data`` — for tests:
   the same diagnostics, returning the data they generated for themselves (see below)
 
 All fail loudly (RuntimeError) if ``libbgc_gpu_diag.so`` or the GPU is missing; there
@@ -102,6 +104,28 @@ def lds(device=0, wgs_per_cu=4, rate_iters=8192, seed=0x5EED):
     twice (a hash pattern, then its inverse), binned by the CU they ran on; then `rate_iters`
     sweeps of 16-byte reads over the array on every CU for the aggregate read rate."""
     return json.loads(native().diag_lds(device, wgs_per_cu, rate_iters, seed))
+
+
+L2_REGION_BYTES = 96 << 10  # BGC_L2_REGION_BYTES: 32 workgroups of an XCD hold 3 MiB of its 4 MiB L2
+L2_SLAB_BYTES = 32 << 10  # a region is 1..4 of these
+# Sweep counts that put each timed launch of cache() at 2-4 ms on the MI355X (tools/probes/cache_rate_probe.py,
+# profiles/cache_diag/cache_rates.json, 12 runs each right after an MFMA check): 4096 sweeps of 96 KiB regions take
+# 3.27-3.44 ms at 30.0-31.6 TB/s, and 128 sweeps of 128 MiB take 2.22-2.51 ms at 6.8-7.7 TB/s.  The whole run is
+# 5.9-6.1 ms of kernels, 6.6-6.8 ms with its allocations.
+L2_SWEEPS = 4096
+IC_BYTES = 128 << 20
+IC_SWEEPS = 128
+
+
+def cache(device=0, rounds=4, region_bytes=L2_REGION_BYTES, l2_sweeps=L2_SWEEPS, ic_bytes=IC_BYTES, ic_sweeps=IC_SWEEPS,
+          seed=0x5EED):
+    """The two SRAM levels between the LDS and HBM.  L2: one workgroup per CU writes and verifies a
+    region of `region_bytes` (32, 64, 96 or 128 KiB) twice per round (a hash pattern, then its
+    inverse) through the L2 of the XCD it runs on, for `rounds` rotations of the regions, binned by
+    XCC; then `l2_sweeps` L1-bypassing sweeps of every region for the aggregate L2 read rate.
+    Infinity Cache (`ic_bytes` 0 turns it off): a buffer of `ic_bytes` is filled, checked word by
+    word, swept `ic_sweeps` times under a 32-bit sum, and checked again."""
+    return json.loads(native().diag_cache(device, rounds, region_bytes, l2_sweeps, ic_bytes, ic_sweeps, seed))
 
 
 def gemm_check(device=0, m=4096, n=4096, k=4096, seed=0x5EED):
@@ -183,7 +207,26 @@ def lds_planted(plants, device=0, wgs_per_cu=1, rate_iters=64, seed=0x5EED):
     return json.loads(native().diag_lds_planted(device, wgs_per_cu, rate_iters, seed, list(plants)))
 
 
+def cache_planted(l2_plants, ic_plants=(), device=0, rounds=1, region_bytes=L2_REGION_BYTES, l2_sweeps=16, ic_bytes=2 << 20,
+                  ic_sweeps=2, seed=0x5EED):
+    """`l2_plants` = [(round, workgroup or ALL_WAVES, pass, word of the region, xor mask), ...]: thread 0
+    of that march workgroup XORs the mask into that word with a plain store after the pass's fill
+    and before its verify.  `ic_plants` = [(when, word of the buffer, xor mask), ...]: applied from
+    the host after the fill (when 0: both checks and the sweeps' sum see it) or after the timed
+    sweeps (when 1: the last check alone)."""
+    return json.loads(native().diag_cache_planted(device, rounds, region_bytes, l2_sweeps, ic_bytes, ic_sweeps, seed,
+                                                  list(l2_plants), list(ic_plants)))
+
+
 MAX_DELAY_TICKS = 10_000_000  # 100 ms of the 100 MHz constant clock
+
+
+def cache_delayed(delays, device=0, rounds=1, region_bytes=L2_REGION_BYTES, l2_sweeps=16, ic_bytes=2 << 20, ic_sweeps=2,
+                  seed=0x5EED):
+    """`delays` = [(workgroup or ALL_WAVES, ticks), ...]: in the timed L2 rate launch that workgroup
+    waits `ticks` of the 100 MHz constant clock after its loop and before it reads its end time.  No
+    value is touched; the time shows in l2_read_tbps, xcc_us, slowest_xcc and xcc_balance."""
+    return json.loads(native().diag_cache_delayed(device, rounds, region_bytes, l2_sweeps, ic_bytes, ic_sweeps, seed, list(delays)))
 
 
 def mfma_delayed(delays, device=0, waves_per_cu=1, iters=64, seed=0x5EED):
@@ -270,6 +313,14 @@ def lds_data(wg, pass_, grid, device=0, seed=0x5EED):
     """The LDS_WORDS words that workgroup `wg` of a march of `grid` workgroups holds after pass
     `pass_` (0: the pattern, 1: its inverse), as uint32."""
     return np.frombuffer(native().diag_lds_data(device, seed, wg, pass_, grid), dtype="<u4")
+
+
+def cache_data(passes, device=0, rounds=1, region_bytes=L2_REGION_BYTES, l2_sweeps=16, ic_bytes=2 << 20, ic_sweeps=2, seed=0x5EED):
+    """(result, the L2 buffer as uint32 [cus, region words] as the march left it, its last round ended
+    after `passes` (1 or 2) passes, the Infinity-Cache buffer as the last check saw it as uint32)"""
+    r, l2, ic = native().diag_cache_data(device, rounds, region_bytes, passes, l2_sweeps, ic_bytes, ic_sweeps, seed)
+    r = json.loads(r)
+    return r, np.frombuffer(l2, dtype="<u4").reshape(r["cus"], region_bytes // 4), np.frombuffer(ic, dtype="<u4")
 
 
 def _bf16_bytes(x):

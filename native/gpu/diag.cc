@@ -214,6 +214,51 @@ json::Value to_json(int device, const bgc_lds_result& r) {
                               {"passed", clean && r.rate_ok != 0}});
 }
 
+json::Value to_json(int device, const bgc_cache_result& r) {
+  char l2_bits[16], ic_bits[16];
+  std::snprintf(l2_bits, sizeof(l2_bits), "0x%08x", r.l2_bad_bits);
+  std::snprintf(ic_bits, sizeof(ic_bits), "0x%08x", r.ic_bad_bits);
+  const bool l2_clean = r.l2_mismatches == 0, ic_clean = r.ic_mismatches == 0, ic_ran = r.ic_bytes != 0;
+  // the per-XCC arrays end at the highest XCC that ran a workgroup: a partitioned device has fewer than 8
+  int xccs = 0;
+  for (int x = 0; x < 8; ++x) {
+    if (r.xcc_wgs[x] > 0 || r.xcc_mismatches[x] > 0) xccs = x + 1;
+  }
+  json::Value mism = json::Value::array(), wgs = json::Value::array(), us = json::Value::array();
+  for (int x = 0; x < xccs; ++x) {
+    mism.push_back(static_cast<unsigned long long>(r.xcc_mismatches[x]));
+    wgs.push_back(r.xcc_wgs[x]);
+    us.push_back(r.xcc_us[x]);
+  }
+  return json::Value::object({{"device", device},
+                              {"cus", r.cus},
+                              {"xccs_seen", r.xccs_seen},
+                              {"rounds", r.rounds},
+                              {"region_bytes", static_cast<unsigned long long>(r.region_bytes)},
+                              {"l2_words_checked", static_cast<unsigned long long>(r.l2_words_checked)},
+                              {"l2_mismatches", static_cast<unsigned long long>(r.l2_mismatches)},
+                              {"l2_bad_xccs", r.l2_bad_xccs},
+                              {"xcc_mismatches", mism},
+                              {"first_bad_xcc", l2_clean ? json::Value() : json::Value(r.first_bad_xcc)},
+                              {"first_bad_word", l2_clean ? json::Value() : json::Value(static_cast<unsigned long long>(r.first_bad_word))},
+                              {"l2_bad_bits", l2_clean ? json::Value() : json::Value(std::string(l2_bits))},
+                              {"l2_read_tbps", r.l2_read_tbps},
+                              {"l2_rate_ok", r.l2_rate_ok != 0},
+                              {"xcc_wgs", wgs},
+                              {"xcc_us", us},
+                              {"slowest_xcc", r.slowest_xcc},
+                              {"xcc_balance", r.xcc_balance},
+                              {"ic_bytes", static_cast<unsigned long long>(r.ic_bytes)},
+                              {"ic_words_checked", static_cast<unsigned long long>(r.ic_words_checked)},
+                              {"ic_mismatches", static_cast<unsigned long long>(r.ic_mismatches)},
+                              {"ic_first_bad_word", ic_clean ? json::Value() : json::Value(static_cast<unsigned long long>(r.ic_first_bad_word))},
+                              {"ic_bad_bits", ic_clean ? json::Value() : json::Value(std::string(ic_bits))},
+                              {"ic_read_tbps", ic_ran ? json::Value(r.ic_read_tbps) : json::Value()},
+                              {"ic_rate_ok", r.ic_rate_ok != 0},
+                              {"elapsed_ms", r.elapsed_ms},
+                              {"passed", l2_clean && ic_clean && r.l2_rate_ok != 0 && r.ic_rate_ok != 0}});
+}
+
 json::Value to_json(int device, const bgc_pcie_result& r) {
   return json::Value::object({{"device", device}, {"bytes", static_cast<unsigned long long>(r.bytes)},
                               {"iters", r.iters}, {"h2d_gbps", r.h2d_gbps}, {"d2h_gbps", r.d2h_gbps},
@@ -273,6 +318,10 @@ json::Value Diag::mfma_classic(int device, int waves_per_cu, int throughput_iter
 
 json::Value Diag::lds(int device, int wgs_per_cu, int rate_iters, uint32_t seed) {
   return call("lds diag", lds_, device, wgs_per_cu, rate_iters, seed);
+}
+
+json::Value Diag::cache(int device, int rounds, uint32_t region_bytes, int l2_sweeps, uint64_t ic_bytes, int ic_sweeps, uint32_t seed) {
+  return call("cache diag", cache_, device, rounds, region_bytes, l2_sweeps, ic_bytes, ic_sweeps, seed);
 }
 
 json::Value Diag::pcie(int device, uint64_t bytes, int iters, uint32_t seed) {

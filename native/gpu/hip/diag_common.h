@@ -1,5 +1,6 @@
-// Shared by the diagnostics' sources (gpu_diag.hip, hbm.hip, mfma.hip, lds.hip, gemm_soak.hip): vector
-// types, the hash, the CU a wave runs on, the last-error string and the host helpers every entry point uses.
+// Shared by the diagnostics' sources (gpu_diag.hip, hbm.hip, mfma.hip, lds.hip, cache.hip, gemm_soak.hip): vector
+// types, the hash, the CU a wave runs on, the marches' pattern and wrong-word record, the delay plants' wait, the
+// last-error string and the host helpers every entry point uses.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -46,6 +47,44 @@ __device__ __forceinline__ uint32_t cu_key() {
   uint32_t se = (hwid >> 13) & 0x7;
   return ((xcc & 0x7) << 8) | (se << 5) | (sh << 4) | cu;
 }
+
+// The XCC (0..7) a wave runs on: the owner of the L2 it reads and writes through.
+__device__ __forceinline__ uint32_t xcc_id() { return cu_key() >> 8; }
+
+// A delay plant's wait (gpu_diag.h): until `ticks` of the constant clock have passed since this
+// point.  The clock difference is the loop's only exit condition, so it ends after `ticks` (checked
+// on the host) whatever else happens.
+__device__ __forceinline__ void wait_ticks(uint32_t ticks) {
+  const uint64_t t0 = wall_clock64();
+  while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
+}
+
+// words 4 e .. 4 e + 3 of a hash pattern with seed s (mix32(word ^ s)), XOR `inv` (0, or ~0 for the inverse)
+__device__ __forceinline__ u32x4 pattern16(uint32_t e, uint32_t s, uint32_t inv) {
+  const uint32_t w = 4 * e;
+  return u32x4{mix32(w ^ s) ^ inv, mix32((w + 1) ^ s) ^ inv, mix32((w + 2) ^ s) ^ inv, mix32((w + 3) ^ s) ^ inv};
+}
+
+// a thread's (then a wave's, then a workgroup's) wrong words of a march
+struct BadWords {
+  unsigned count = 0, bits = 0, first = ~0u;
+  __device__ __forceinline__ void check(uint32_t word, uint32_t expected, uint32_t found) {
+    if (expected != found) {
+      count++;
+      bits |= expected ^ found;
+      first = min(first, word);
+    }
+  }
+  __device__ __forceinline__ void merge(unsigned c, unsigned b, unsigned f) {
+    count += c;
+    bits |= b;
+    first = min(first, f);
+  }
+  // the sum over the wave, in its lane 0
+  __device__ __forceinline__ void merge_wave() {
+    for (int off = 32; off > 0; off >>= 1) merge(__shfl_down(count, off, 64), __shfl_down(bits, off, 64), __shfl_down(first, off, 64));
+  }
+};
 
 #define HIP_TRY(expr)                                                                  \
   do {                                                                                  \

@@ -80,6 +80,16 @@ extern "C" {
 //    pairwise distinct, so no word equals the same word of any other workgroup: a write that lands
 //    at the wrong address reads back as a wrong value elsewhere, what the previous workgroup left on
 //    the CU cannot pass, and every cell is checked holding both 0 and 1.
+//  * L2 march and rate (bgc_diag_cache).  The L2 buffer is `grid` regions of region_words =
+//    region_bytes / 4 32-bit words, `grid` being the device's CU count.  In round r (0-based) of the
+//    march, workgroup b works on region (b + r) mod grid with s = mix32(seed + (r * grid + b + 1) *
+//    0x9e3779b9); word j of the region holds mix32(j ^ s) in pass 0 and its inverse in pass 1.  The
+//    rate phase uses the seed of round `rounds`: workgroup b fills region b with mix32(j ^ s),
+//    s = mix32(seed + (rounds * grid + b + 1) * 0x9e3779b9).  The seeds of one run are pairwise
+//    distinct, so what another round or another workgroup left in a region cannot pass.  A word of
+//    the march is named by its index in the whole buffer, region * region_words + j.
+//  * Infinity Cache (bgc_diag_cache).  Word i of the buffer holds mix32(u32(i) ^ mix32(~seed)); S is
+//    the sum of all its words modulo 2^32.
 
 typedef struct {
   uint64_t bytes;          // buffer size tested
@@ -279,6 +289,48 @@ typedef struct {
 // 16- and 8-byte loads), attributed to (XCC, SE, SH, CU); then `rate_iters` (1..65536) sweeps of
 // conflict-free 16-byte reads over the array by one workgroup per CU, for the LDS read rate.
 int bgc_diag_lds(int device, int wgs_per_cu, int rate_iters, uint32_t seed, bgc_lds_result* out);
+#define BGC_L2_REGION_BYTES (96u << 10)  // default region of an L2 workgroup: 32 of them hold 3 MiB of an XCD's 4 MiB
+#define BGC_L2_SLAB_BYTES (32u << 10)    // a region is 1..4 of these: 256 threads x 16 B x 8 loads in flight
+typedef struct {
+  int cus;                     // CUs of the device: workgroups of every L2 launch, regions of the L2 buffer
+  int xccs_seen;               // distinct XCCs that ran a march workgroup
+  int rounds;
+  uint32_t region_bytes;
+  uint64_t l2_words_checked;   // 2 * region words per workgroup and round
+  uint64_t l2_mismatches;      // 32-bit words that read back wrong from L2, both passes, all rounds
+  int l2_bad_xccs;             // XCCs with >= 1 mismatch
+  uint64_t xcc_mismatches[8];  // by the XCC the workgroup ran on
+  int first_bad_xcc;           // lowest bad XCC, -1 if none
+  uint64_t first_bad_word;     // lowest failing word on that XCC, as an index in the whole L2 buffer
+  uint32_t l2_bad_bits;        // OR of expected ^ found over all failures
+  double l2_read_tbps;         // rate phase: bytes read through L2 / device time, all XCCs
+  int l2_rate_ok;              // every thread's sum matched
+  int xcc_wgs[8];              // rate workgroups that ran on each XCC
+  double xcc_us[8];            // mean time of their loops (constant 100 MHz clock)
+  int slowest_xcc;             // -1 if none ran
+  double xcc_balance;          // fastest / slowest XCC mean loop time (1.0 = balanced)
+  uint64_t ic_bytes;           // Infinity-Cache phase: buffer size, 0 when the phase is off
+  uint64_t ic_words_checked;   // 2 * ic_bytes / 4: once after the fill, once after the timed sweeps
+  uint64_t ic_mismatches;      // both checks summed
+  uint64_t ic_first_bad_word;  // lowest failing 32-bit word of the buffer (UINT64_MAX if none)
+  uint32_t ic_bad_bits;
+  double ic_read_tbps;         // bytes of the timed sweeps / device time
+  int ic_rate_ok;              // their 32-bit total was ic_sweeps * S (1 when the phase is off)
+  double elapsed_ms;
+} bgc_cache_result;
+
+// The two SRAM levels between the LDS and HBM, which the other checks pass through without
+// holding anything in them: each XCD's 4 MiB L2 and the 256 MiB Infinity Cache.
+//  * L2: one workgroup per CU owns a region of `region_bytes` (32, 64, 96 or 128 KiB) of a buffer
+//    sized for all of them.  `rounds` (1..16) march launches, each a fill with plain stores, a
+//    verify with L1-bypassing loads, then the inverse (dword stores, 8-byte loads), attributed to
+//    the XCC the workgroup ran on; the regions rotate over the workgroups from round to round.  Then
+//    `l2_sweeps` (1..65536) L1-bypassing sweeps of each region, for the aggregate L2 read rate.
+//  * Infinity Cache: off when `ic_bytes` is 0, else a buffer of `ic_bytes` (a multiple of 1 MiB, at
+//    most 1 GiB) is filled, checked word by word, swept `ic_sweeps` (1..4096) times under a 32-bit
+//    sum with every sweep's reads coming from another XCD than the last, and checked again.
+int bgc_diag_cache(int device, int rounds, uint32_t region_bytes, int l2_sweeps, uint64_t ic_bytes, int ic_sweeps,
+                   uint32_t seed, bgc_cache_result* out);
 // ---------------------------------------------------------------------------------------------
 // Planted variants: FOR TESTS ONLY.  Each runs the same implementation as the entry point it is
 // named after, with a list of deliberately wrong values ("plants") written into the diagnostic's
@@ -422,6 +474,40 @@ typedef struct {
 int bgc_diag_lds_planted(int device, int wgs_per_cu, int rate_iters, uint32_t seed, const bgc_lds_plant* plants, int n,
                          bgc_lds_result* out);
 
+// region[word] ^= xor_mask in march workgroup `wg` (or in every one, BGC_PLANT_ALL_WAVES) of round
+// `round`, by its thread 0 with a plain store after pass `pass`'s fill barrier and before its verify,
+// so the line changes in the L2 that holds it.  round < rounds, pass 0 or 1, word < region_bytes / 4,
+// a non-zero mask, wg below the grid (the CU count).  The rate phase takes no value plant.
+typedef struct {
+  int round;
+  int wg;
+  int pass;
+  uint32_t word;
+  uint32_t xor_mask;
+} bgc_l2_plant;
+// buffer[word] ^= xor_mask from the host: `when` 0 after the fill and before the first check (so
+// both checks and the sweeps' sum see it), 1 after the timed sweeps and before the last check.
+// word < ic_bytes / 4, a non-zero mask.
+typedef struct {
+  int when;
+  uint64_t word;
+  uint32_t xor_mask;
+} bgc_ic_plant;
+int bgc_diag_cache_planted(int device, int rounds, uint32_t region_bytes, int l2_sweeps, uint64_t ic_bytes, int ic_sweeps,
+                           uint32_t seed, const bgc_l2_plant* l2_plants, int n_l2, const bgc_ic_plant* ic_plants, int n_ic,
+                           bgc_cache_result* out);
+// Workgroup `wg` (or every one, BGC_PLANT_ALL_WAVES) of the timed L2 rate launch waits `ticks`
+// (1..BGC_DIAG_MAX_DELAY_TICKS) of the constant clock after its loop and before it reads its end time,
+// as the matrix-core delay plants below do.  The warm-up launch, the march and the Infinity-Cache
+// phase take none, and no value is touched: the time shows in l2_read_tbps, xcc_us, slowest_xcc and
+// xcc_balance only.
+typedef struct {
+  int wg;
+  uint32_t ticks;
+} bgc_cache_delay_plant;
+int bgc_diag_cache_delayed(int device, int rounds, uint32_t region_bytes, int l2_sweeps, uint64_t ic_bytes, int ic_sweeps,
+                           uint32_t seed, const bgc_cache_delay_plant* delays, int n, bgc_cache_result* out);
+
 // ---------------------------------------------------------------------------------------------
 // Generated data: FOR TESTS ONLY, never loaded by the node agent or the diag worker.  Each runs
 // the same implementation as the entry point it is named after and then copies the data that
@@ -475,6 +561,15 @@ int bgc_diag_mfma_classic_tile(int device, int path, uint32_t seed, uint32_t til
 // The march with `grid` (1..4096) workgroups; workgroup `wg` (< grid) copies its whole array, as it
 // is after pass `pass`'s (0 or 1) verify, to `data` (BGC_LDS_WORDS words).
 int bgc_diag_lds_data(int device, uint32_t seed, int wg, int pass, int grid, void* data);
+// bgc_diag_cache with the march ended after `passes` (1 or 2) passes of its last round; then the
+// whole L2 buffer as the march left it (out->cus * region_bytes bytes) to `l2_data`, which holds
+// `l2_capacity` bytes, and the Infinity-Cache buffer as the last check saw it (ic_bytes) to
+// `ic_data`, which may be null when ic_bytes is 0.  l2_capacity + ic_bytes may not exceed
+// BGC_DIAG_MAX_DATA_BYTES; a device whose L2 buffer exceeds l2_capacity is refused once its CU count
+// is known.
+int bgc_diag_cache_data(int device, int rounds, uint32_t region_bytes, int passes, int l2_sweeps, uint64_t ic_bytes,
+                        int ic_sweeps, uint32_t seed, void* l2_data, uint64_t l2_capacity, void* ic_data,
+                        bgc_cache_result* out);
 
 // PCI bus id of a HIP device ("0000:05:00.0", lower-case hex) — the key the node agent and
 // the RCCL probe use to match a HIP device (renumbered inside a container) to amdsmi.

@@ -6,6 +6,8 @@
 //  * mfma.hip: the per-CU bf16, MX fp8/fp4 and fp16/int8/fp32/fp64 matrix-core checks and throughput kernels, the
 //    burn-in loop that runs them back to back, and the one-wave GEMMs on caller operands;
 //  * lds.hip: the per-CU march test of the whole Local Data Share and its read rate;
+//  * cache.hip: the per-XCC march through every XCD's L2 with its read rate, and the Infinity Cache's
+//    pattern check and read rate;
 //  * gemm_soak.hip: the ABFT-checked LDS-tiled GEMMs (gemm_soak and the 8-phase gemm_pingpong).
 // The design notes in those files follow the CDNA4 guides (cdna_hip_programming.md,
 // MI355X_MICROARCH.md).

@@ -50,12 +50,6 @@ static_assert(kRateThreads == 256 || kRateThreads == 512, "256 or 512 threads");
 
 __device__ __forceinline__ uint32_t wg_seed(uint32_t seed, uint32_t wg) { return mix32(seed + (wg + 1) * 0x9e3779b9U); }
 
-// words 4 e .. 4 e + 3 of the pattern, XOR `inv` (0, or ~0 for the inverse)
-__device__ __forceinline__ u32x4 pattern16(uint32_t e, uint32_t s, uint32_t inv) {
-  const uint32_t w = 4 * e;
-  return u32x4{mix32(w ^ s) ^ inv, mix32((w + 1) ^ s) ^ inv, mix32((w + 2) ^ s) ^ inv, mix32((w + 3) ^ s) ^ inv};
-}
-
 // A CU's bins (index: cu_key()).  `first` starts at ~0.
 struct MarchBin {
   unsigned checked, bad, bits, first;
@@ -63,23 +57,6 @@ struct MarchBin {
 struct RateBin {
   unsigned long long ticks;
   unsigned wgs, pad;
-};
-
-// a thread's (then a wave's, then a workgroup's) wrong words
-struct BadWords {
-  unsigned count = 0, bits = 0, first = ~0u;
-  __device__ __forceinline__ void check(uint32_t word, uint32_t expected, uint32_t found) {
-    if (expected != found) {
-      count++;
-      bits |= expected ^ found;
-      first = min(first, word);
-    }
-  }
-  __device__ __forceinline__ void merge(unsigned c, unsigned b, unsigned f) {
-    count += c;
-    bits |= b;
-    first = min(first, f);
-  }
 };
 
 // Test plants and the generated-data copy (gpu_diag.h).  lds_march ends in a pack `Extras... extras`:
@@ -156,9 +133,7 @@ __global__ __launch_bounds__(kBlock) void lds_march(uint32_t seed, MarchBin* __r
   }
   after_verify(lds, 1, extras...);
   // the workgroup's outcome: wave sums by shuffle, then through the array, which is free now
-  for (int off = 32; off > 0; off >>= 1) {
-    bad.merge(__shfl_down(bad.count, off, 64), __shfl_down(bad.bits, off, 64), __shfl_down(bad.first, off, 64));
-  }
+  bad.merge_wave();
   __syncthreads();
   if ((t & 63) == 0) {
     words[3 * (t >> 6)] = bad.count;

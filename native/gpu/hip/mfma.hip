@@ -301,8 +301,8 @@ template <class Acc>
 __device__ __forceinline__ void plant(Acc (&)[4], uint32_t /*wave*/, int /*lane*/, DelayPlants) {}  // no values
 
 // throughput phase, at the same point: the wave waits for the largest `ticks` of the delay plants
-// that name it, counted on the constant clock from here.  The loop's only exit condition is the clock
-// difference, so it ends after `ticks` (at most BGC_DIAG_MAX_DELAY_TICKS, checked on the host).
+// that name it, counted on the constant clock from here (wait_ticks: it ends after `ticks`, at most
+// BGC_DIAG_MAX_DELAY_TICKS, checked on the host).
 __device__ __forceinline__ void delay(uint32_t /*wave*/) {}
 __device__ __forceinline__ void delay(uint32_t /*wave*/, RatePlants) {}
 __device__ __forceinline__ void delay(uint32_t wave, DelayPlants pl) {
@@ -311,9 +311,7 @@ __device__ __forceinline__ void delay(uint32_t wave, DelayPlants pl) {
     const bgc_mfma_delay_plant p = pl.p[j];
     if (p.wave == BGC_PLANT_ALL_WAVES || static_cast<uint32_t>(p.wave) == wave) ticks = max(ticks, p.ticks);
   }
-  ticks = __builtin_amdgcn_readfirstlane(ticks);  // the same in every lane of the wave
-  const uint64_t t0 = wall_clock64();
-  while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
+  wait_ticks(__builtin_amdgcn_readfirstlane(ticks));  // the same in every lane of the wave
 }
 
 // ---------------------------------------------------------------------------

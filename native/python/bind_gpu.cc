@@ -252,6 +252,11 @@ void register_gpu(py::module_& m) {
   m.def("diag_lds", [](int device, int wgs_per_cu, int rate_iters, unsigned seed) {
     return dump_nogil([&] { return Diag::instance().lds(device, wgs_per_cu, rate_iters, seed); });
   }, py::arg("device"), py::arg("wgs_per_cu") = 4, py::arg("rate_iters") = 8192, py::arg("seed") = 0x5eed);
+  m.def("diag_cache", [](int device, int rounds, unsigned region_bytes, int l2_sweeps, unsigned long long ic_bytes, int ic_sweeps,
+                         unsigned seed) {
+    return dump_nogil([&] { return Diag::instance().cache(device, rounds, region_bytes, l2_sweeps, ic_bytes, ic_sweeps, seed); });
+  }, py::arg("device"), py::arg("rounds") = 4, py::arg("region_bytes") = BGC_L2_REGION_BYTES, py::arg("l2_sweeps") = 4096,
+     py::arg("ic_bytes") = 128ULL << 20, py::arg("ic_sweeps") = 128, py::arg("seed") = 0x5eed);
   m.def("diag_gemm", [](int device, int mm, int nn, int kk, const std::string& a, const std::string& b) {
     if (a.size() != static_cast<size_t>(mm) * kk * 2 || b.size() != static_cast<size_t>(kk) * nn * 2) {
       throw std::invalid_argument("A must be M*K and B K*N bf16 values");
@@ -364,6 +369,27 @@ void register_gpu(py::module_& m) {
     for (const auto& [wg, pass, word, mask] : plants) p.push_back({wg, pass, word, mask});
     return planted("lds diag", BGC_DIAG_ENTRY(bgc_diag_lds_planted), device, wgs_per_cu, rate_iters, seed, p.data(), count(p));
   }, py::arg("device"), py::arg("wgs_per_cu"), py::arg("rate_iters"), py::arg("seed"), py::arg("plants"));
+  // L2 plants (round, wg or -1, pass, word of the region, mask) and Infinity-Cache plants (when, word of the buffer, mask)
+  m.def("diag_cache_planted", [](int device, int rounds, unsigned region_bytes, int l2_sweeps, u64 ic_bytes, int ic_sweeps, unsigned seed,
+                                 const std::vector<std::tuple<int, int, int, unsigned, unsigned>>& l2_plants,
+                                 const std::vector<std::tuple<int, u64, unsigned>>& ic_plants) {
+    std::vector<bgc_l2_plant> l2;
+    std::vector<bgc_ic_plant> ic;
+    for (const auto& [round, wg, pass, word, mask] : l2_plants) l2.push_back({round, wg, pass, word, mask});
+    for (const auto& [when, word, mask] : ic_plants) ic.push_back({when, word, mask});
+    return planted("cache diag", BGC_DIAG_ENTRY(bgc_diag_cache_planted), device, rounds, region_bytes, l2_sweeps, ic_bytes, ic_sweeps,
+                   seed, l2.data(), count(l2), ic.data(), count(ic));
+  }, py::arg("device"), py::arg("rounds"), py::arg("region_bytes"), py::arg("l2_sweeps"), py::arg("ic_bytes"), py::arg("ic_sweeps"),
+     py::arg("seed"), py::arg("l2_plants"), py::arg("ic_plants"));
+  // (workgroup or -1, ticks of the constant clock) in the timed L2 rate launch
+  m.def("diag_cache_delayed", [](int device, int rounds, unsigned region_bytes, int l2_sweeps, u64 ic_bytes, int ic_sweeps, unsigned seed,
+                                 const std::vector<std::tuple<int, unsigned>>& delays) {
+    std::vector<bgc_cache_delay_plant> d;
+    for (const auto& [wg, ticks] : delays) d.push_back({wg, ticks});
+    return planted("cache diag", BGC_DIAG_ENTRY(bgc_diag_cache_delayed), device, rounds, region_bytes, l2_sweeps, ic_bytes, ic_sweeps,
+                   seed, d.data(), count(d));
+  }, py::arg("device"), py::arg("rounds"), py::arg("region_bytes"), py::arg("l2_sweeps"), py::arg("ic_bytes"), py::arg("ic_sweeps"),
+     py::arg("seed"), py::arg("delays"));
   // Delay plants: (wave or -1, ticks of the constant clock) in the timed throughput launch; and a burn
   // whose launches from `first_delayed_launch` on have every wave delayed by `ticks`.
   m.def("diag_mfma_delayed", [](int device, int waves_per_cu, int iters, unsigned seed,
@@ -468,6 +494,23 @@ void register_gpu(py::module_& m) {
     }
     return py::bytes(data);
   }, py::arg("device"), py::arg("seed"), py::arg("wg"), py::arg("pass"), py::arg("grid"));
+  // the result, the L2 buffer (cus regions) and the Infinity-Cache buffer, as bytes.  The destination holds the L2
+  // buffer of up to 512 CUs; a request that exceeds the library's cap with it gets empty buffers and is refused there.
+  m.def("diag_cache_data", [](int device, int rounds, unsigned region_bytes, int passes, int l2_sweeps, u64 ic_bytes, int ic_sweeps,
+                              unsigned seed) {
+    const u64 capacity = region_bytes <= 4 * BGC_L2_SLAB_BYTES ? 512ULL * region_bytes : 0;
+    const bool fits = ic_bytes <= BGC_DIAG_MAX_DATA_BYTES && capacity + ic_bytes <= BGC_DIAG_MAX_DATA_BYTES;
+    std::string l2(fits ? capacity : 0, '\0'), ic(fits ? ic_bytes : 0, '\0');
+    Value v;
+    {
+      py::gil_scoped_release nogil;
+      v = Diag::instance().call("cache diag", BGC_DIAG_ENTRY(bgc_diag_cache_data), device, rounds, region_bytes, passes, l2_sweeps,
+                                ic_bytes, ic_sweeps, seed, static_cast<void*>(l2.data()), capacity, static_cast<void*>(ic.data()));
+    }
+    l2.resize(static_cast<size_t>(v.get("cus").as_int()) * region_bytes);
+    return py::make_tuple(v.dump(), py::bytes(l2), py::bytes(ic));
+  }, py::arg("device"), py::arg("rounds"), py::arg("region_bytes"), py::arg("passes"), py::arg("l2_sweeps"), py::arg("ic_bytes"),
+     py::arg("ic_sweeps"), py::arg("seed"));
 #undef BGC_DIAG_ENTRY
   m.def("pcie_check", [](std::shared_ptr<PyBackend> b, int index, int hip_device, unsigned long long bytes, unsigned seed) {
     return dump_nogil([&] {
