@@ -1,4 +1,4 @@
-"""HIP/CDNA4 GPU health kernels (native/gpu/hip/: hbm.hip, mfma.hip, lds.hip, cache.hip, gemm_soak.hip) exposed to Python.
+"""HIP/CDNA4 GPU health kernels (native/gpu/hip/: hbm.hip, mfma.hip, lds.hip, cache.hip, valu.hip, gemm_soak.hip) exposed to Python.
 
 These are the only compute kernels in the framework: the reference controller has none
 (SURVEY §2.5).  They back the node agent's diagnostics before a GPU is advertised
@@ -16,6 +16,8 @@ These are the only compute kernels in the framework: the reference controller ha
   the CU, then the aggregate LDS read rate
 * ``cache(device)``     — a march through every XCD's L2 (4 MiB each), attributed to the XCC, and the
   aggregate L2 read rate; then a pattern check and the read rate of the 256 MiB Infinity Cache
+* ``valu(device)``      — the vector ALU's integer, fp32, fp16, fp64, conversion, integer-dot and transcendental
+  instructions on every SIMD, refereed by the host CPU and attributed to CU, SIMD and lane; then the vector rates
 * ``gemm_check(device)``— a bf16 GEMM on the matrix cores checked element by element against
   a double-precision product of the same operands on the host
 * ``gemm_soak(device)`` — the sustained-throughput soak: the 8-phase ping-pong GEMM
@@ -30,11 +32,11 @@ These are the only compute kernels in the framework: the reference controller ha
 * ``pcie(device)``      — host<->device copy bandwidth, pinned
 * ``device_bdf(device)``— the HIP device's PCI address, to match it to amdsmi / kubelet
 * ``hbm_planted``, ``hbm_walk_planted``, ``pcie_planted``, ``mfma_planted``,
-  ``mfma_lowp_planted``, ``mfma_classic_planted``, ``lds_planted``, ``cache_planted``, ``gemm_soak_planted``, ``burn_planted`` — for tests: the same diagnostics with wrong
+  ``mfma_lowp_planted``, ``mfma_classic_planted``, ``lds_planted``, ``cache_planted``, ``valu_planted``, ``gemm_soak_planted``, ``burn_planted`` — for tests: the same diagnostics with wrong
   values planted in their own data, to show that they are detected (see below)
-* ``mfma_delayed``, ``burn_delayed``, ``cache_delayed`` — for tests: the matrix-core throughput, the burn and the L2 rate with
+* ``mfma_delayed``, ``burn_delayed``, ``cache_delayed``, ``valu_delayed`` — for tests: the matrix-core throughput, the burn, the L2 rate and the vector rates with
   chosen waves, launches or workgroups made slow by a known time, to show that it reaches the rates
-* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile``, ``mfma_classic_tile``, ``lds_data``, ``cache_data`` — for tests:
+* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile``, ``mfma_classic_tile``, ``lds_data``, ``cache_data``, ``valu_data``, ``valu_expected`` — for tests:
   the same diagnostics, returning the data they generated for themselves (see below)
 
 All fail loudly (RuntimeError) if ``libbgc_gpu_diag.so`` or the GPU is missing; there
@@ -128,6 +130,41 @@ def cache(device=0, rounds=4, region_bytes=L2_REGION_BYTES, l2_sweeps=L2_SWEEPS,
     return json.loads(native().diag_cache(device, rounds, region_bytes, l2_sweeps, ic_bytes, ic_sweeps, seed))
 
 
+VALU_CLASSES = ("int32", "fp32", "fp16", "fp64", "cvt", "dot", "trans")  # BGC_VALU_*: the order of class_mismatches
+VALU_CLASS_WORDS = (13, 6, 3, 6, 5, 2, 5)  # 32-bit result words of a class per round, 40 in all (BGC_VALU_ROUND_WORDS)
+VALU_ROUND_WORDS = 40
+VALU_RATE_CLASSES = ("fp32", "fp16", "fp64", "int32", "trans")  # BGC_VALU_RATE_*: the order of rate_ms
+# Defaults of valu(), from tools/probes/valu_rate_probe.py on the MI355X (profiles/valu_diag/rates.json, 12 runs per point, each
+# right after an MFMA check).  The rates rise with the iterations until the launch outlasts its ramp: at 2 waves per SIMD, fp32
+# reads 102-106 TF/s at 1024 iterations, 112-117 at 4096 and 115-120 at 16384, where the five timed launches take 0.53-0.59 ms
+# each (trans 1.4 ms).  The whole run is then 3.7-4.2 ms of kernels, 9.1-9.3 ms with its copies and the host referee (14 ms in
+# a fresh process).  More waves per SIMD read more (8: 128-130 TF/s fp32) at 4 times the time and the digests to copy.
+VALU_WAVES_PER_SIMD = 2
+VALU_ROUNDS = 16
+VALU_RATE_ITERS = 16384
+
+
+def _valu_code(names, name):
+    """a class's name, or its number as it is (so a test can pass one out of range)"""
+    return names.index(name) if isinstance(name, str) else name
+
+
+def valu(device=0, waves_per_simd=VALU_WAVES_PER_SIMD, rounds=VALU_ROUNDS, rate_iters=VALU_RATE_ITERS, seed=0x5EED):
+    """The vector ALU: cus * `waves_per_simd` (1..8) workgroups of four waves each run `rounds` (1..64) rounds of a
+    fixed instruction sequence in seven classes (VALU_CLASSES) on per-lane operands and write a digest per lane and
+    class; the host CPU recomputes the six exact classes, judges the transcendentals by the waves' consensus and
+    against libm, and names the CU, SIMD and lane of a wrong value.  Then each rate class (VALU_RATE_CLASSES) runs
+    `rate_iters` (1..65536) iterations of 8 chains per lane: ``fp32_tflops``, ``fp16_tflops``, ``fp64_tflops``,
+    ``int32_tops``, ``trans_tips`` (10^12 v_exp_f32 per second); ``rate_ms`` in that order."""
+    return json.loads(native().diag_valu(device, waves_per_simd, rounds, rate_iters, seed))
+
+
+def valu_trans_ulps():
+    """The accuracy bounds of v_exp_f32, v_log_f32, v_rcp_f32, v_rsq_f32 and v_sqrt_f32 against double-precision
+    libm, in units of the last place of the fp32 result (BGC_VALU_*_ULPS)."""
+    return tuple(native().diag_valu_trans_ulps())
+
+
 def gemm_check(device=0, m=4096, n=4096, k=4096, seed=0x5EED):
     return json.loads(native().diag_gemm_check(device, m, n, k, seed))
 
@@ -218,7 +255,25 @@ def cache_planted(l2_plants, ic_plants=(), device=0, rounds=1, region_bytes=L2_R
                                                   list(l2_plants), list(ic_plants)))
 
 
+def valu_planted(check_plants, rate_plants=(), device=0, waves_per_simd=1, rounds=2, rate_iters=16, seed=0x5EED):
+    """`check_plants` = [(wave or ALL_WAVES, class, round, lane, result word of the class, xor mask), ...]: that wave
+    XORs the mask into that result word before it folds it into the digest.  `rate_plants` = [(wave or ALL_WAVES,
+    rate class, lane, chain, xor mask), ...] do so to the first word of that chain after the loop of that class's
+    timed launch.  Classes by name (VALU_CLASSES, VALU_RATE_CLASSES) or number."""
+    check = [(p[0], _valu_code(VALU_CLASSES, p[1])) + tuple(p[2:]) for p in check_plants]
+    rate = [(p[0], _valu_code(VALU_RATE_CLASSES, p[1])) + tuple(p[2:]) for p in rate_plants]
+    return json.loads(native().diag_valu_planted(device, waves_per_simd, rounds, rate_iters, seed, check, rate))
+
+
 MAX_DELAY_TICKS = 10_000_000  # 100 ms of the 100 MHz constant clock
+
+
+def valu_delayed(delays, device=0, waves_per_simd=1, rounds=2, rate_iters=16, seed=0x5EED):
+    """`delays` = [(wave or ALL_WAVES, rate class, ticks), ...]: in that class's timed rate launch that wave waits
+    `ticks` of the 100 MHz constant clock after its loop and before it reads its end time.  No value is touched;
+    the time shows in the class's rate and rate_ms, in slowest_cu_key and in cu_balance."""
+    return json.loads(native().diag_valu_delayed(device, waves_per_simd, rounds, rate_iters, seed,
+                                                 [(d[0], _valu_code(VALU_RATE_CLASSES, d[1]), d[2]) for d in delays]))
 
 
 def cache_delayed(delays, device=0, rounds=1, region_bytes=L2_REGION_BYTES, l2_sweeps=16, ic_bytes=2 << 20, ic_sweeps=2,
@@ -321,6 +376,32 @@ def cache_data(passes, device=0, rounds=1, region_bytes=L2_REGION_BYTES, l2_swee
     r, l2, ic = native().diag_cache_data(device, rounds, region_bytes, passes, l2_sweeps, ic_bytes, ic_sweeps, seed)
     r = json.loads(r)
     return r, np.frombuffer(l2, dtype="<u4").reshape(r["cus"], region_bytes // 4), np.frombuffer(ic, dtype="<u4")
+
+
+VALU_WAVE = np.dtype([("cu_key", "<i4"), ("simd", "<i4"), ("rate_cu_key", "<i4", 5), ("digests", "<u4", (7, 64)), ("raw", "<u4", (64, VALU_ROUND_WORDS, 64))])
+
+
+def _valu_wave(data, rounds):
+    w = np.frombuffer(data, dtype=VALU_WAVE)[0]
+    return {"cu_key": int(w["cu_key"]), "simd": int(w["simd"]), "rate_cu_key": [int(k) for k in w["rate_cu_key"]], "digests": w["digests"], "raw": w["raw"][:rounds]}
+
+
+def valu_data(wave, check_plants=(), rate_plants=(), delays=(), device=0, waves_per_simd=1, rounds=2, rate_iters=16, seed=0x5EED):
+    """(result, check wave `wave` of that run) with the plants of valu_planted and the delays of valu_delayed applied.
+    The wave: ``cu_key`` and ``simd`` where it ran in the check launch, ``rate_cu_key`` the CU it ran on in each rate
+    class's timed launch (a wave is placed anew in every launch, and in every run), ``digests`` [class, lane] as it
+    wrote them, ``raw`` [round, result word of the round, lane] as it folded them, all uint32."""
+    check = [(p[0], _valu_code(VALU_CLASSES, p[1])) + tuple(p[2:]) for p in check_plants]
+    rate = [(p[0], _valu_code(VALU_RATE_CLASSES, p[1])) + tuple(p[2:]) for p in rate_plants]
+    slow = [(d[0], _valu_code(VALU_RATE_CLASSES, d[1]), d[2]) for d in delays]
+    r, data = native().diag_valu_data(device, waves_per_simd, rounds, rate_iters, seed, wave, check, rate, slow)
+    return json.loads(r), _valu_wave(data, rounds)
+
+
+def valu_expected(rounds, seed=0x5EED):
+    """What the host referee expects of every wave, shaped as valu_data's wave (``cu_key``, ``simd`` and ``rate_cu_key`` -1; the
+    trans words are double-precision libm rounded to fp32, which no digest is compared with).  Needs no GPU."""
+    return _valu_wave(native().diag_valu_expected(seed, rounds), rounds)
 
 
 def _bf16_bytes(x):

@@ -259,6 +259,48 @@ json::Value to_json(int device, const bgc_cache_result& r) {
                               {"passed", l2_clean && ic_clean && r.l2_rate_ok != 0 && r.ic_rate_ok != 0}});
 }
 
+json::Value to_json(int device, const bgc_valu_result& r) {
+  static const char* const kClasses[BGC_VALU_CLASSES] = {"int32", "fp32", "fp16", "fp64", "cvt", "dot", "trans"};
+  json::Value by_class = json::Value::array(), rate_ms = json::Value::array();
+  uint64_t mism = 0;
+  for (int c = 0; c < BGC_VALU_CLASSES; ++c) {
+    by_class.push_back(static_cast<unsigned long long>(r.mismatches[c]));
+    mism += r.mismatches[c];
+  }
+  for (int c = 0; c < BGC_VALU_RATE_CLASSES; ++c) rate_ms.push_back(r.rate_ms[c]);
+  char lanes[24];
+  std::snprintf(lanes, sizeof(lanes), "0x%016llx", static_cast<unsigned long long>(r.bad_lanes));
+  const bool clean = mism == 0;
+  return json::Value::object({{"device", device},
+                              {"cus", r.cus},
+                              {"cus_seen", r.cus_seen},
+                              {"simds_seen", r.simds_seen},
+                              {"values_checked", static_cast<unsigned long long>(r.values_checked)},
+                              {"class_mismatches", by_class},  // int32, fp32, fp16, fp64, cvt, dot, trans
+                              {"mismatches", static_cast<unsigned long long>(mism)},
+                              {"consensus_ok", r.consensus_ok != 0},
+                              {"trans_out_of_bound", static_cast<unsigned long long>(r.trans_out_of_bound)},
+                              {"bad_cus", r.bad_cus},
+                              {"bad_simds", r.bad_simds},
+                              {"bad_cu_keys", bad_cu_keys(r)},
+                              {"first_bad_cu_key", clean ? json::Value() : json::Value(r.first_bad_cu_key)},
+                              {"first_bad_simd", clean ? json::Value() : json::Value(r.first_bad_simd)},
+                              {"first_bad_lane", clean ? json::Value() : json::Value(r.first_bad_lane)},
+                              {"first_bad_class", clean ? json::Value() : json::Value(std::string(kClasses[r.first_bad_class]))},
+                              {"bad_lanes", clean ? json::Value() : json::Value(std::string(lanes))},
+                              {"fp32_tflops", r.rate[BGC_VALU_RATE_FP32]},
+                              {"fp16_tflops", r.rate[BGC_VALU_RATE_FP16]},
+                              {"fp64_tflops", r.rate[BGC_VALU_RATE_FP64]},
+                              {"int32_tops", r.rate[BGC_VALU_RATE_INT32]},
+                              {"trans_tips", r.rate[BGC_VALU_RATE_TRANS]},
+                              {"rate_ms", rate_ms},  // fp32, fp16, fp64, int32, trans
+                              {"rate_ok", r.rate_ok != 0},
+                              {"slowest_cu_key", r.slowest_cu_key},
+                              {"cu_balance", r.cu_balance},
+                              {"elapsed_ms", r.elapsed_ms},
+                              {"passed", clean && r.consensus_ok != 0 && r.trans_out_of_bound == 0 && r.rate_ok != 0}});
+}
+
 json::Value to_json(int device, const bgc_pcie_result& r) {
   return json::Value::object({{"device", device}, {"bytes", static_cast<unsigned long long>(r.bytes)},
                               {"iters", r.iters}, {"h2d_gbps", r.h2d_gbps}, {"d2h_gbps", r.d2h_gbps},
@@ -322,6 +364,10 @@ json::Value Diag::lds(int device, int wgs_per_cu, int rate_iters, uint32_t seed)
 
 json::Value Diag::cache(int device, int rounds, uint32_t region_bytes, int l2_sweeps, uint64_t ic_bytes, int ic_sweeps, uint32_t seed) {
   return call("cache diag", cache_, device, rounds, region_bytes, l2_sweeps, ic_bytes, ic_sweeps, seed);
+}
+
+json::Value Diag::valu(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed) {
+  return call("valu diag", valu_, device, waves_per_simd, rounds, rate_iters, seed);
 }
 
 json::Value Diag::pcie(int device, uint64_t bytes, int iters, uint32_t seed) {

@@ -1,4 +1,4 @@
-// Shared by the diagnostics' sources (gpu_diag.hip, hbm.hip, mfma.hip, lds.hip, cache.hip, gemm_soak.hip): vector
+// Shared by the diagnostics' sources (gpu_diag.hip, hbm.hip, mfma.hip, lds.hip, cache.hip, valu.hip, gemm_soak.hip): vector
 // types, the hash, the CU a wave runs on, the marches' pattern and wrong-word record, the delay plants' wait, the
 // last-error string and the host helpers every entry point uses.
 #pragma once
@@ -46,6 +46,14 @@ __device__ __forceinline__ uint32_t cu_key() {
   uint32_t sh = (hwid >> 12) & 0x1;
   uint32_t se = (hwid >> 13) & 0x7;
   return ((xcc & 0x7) << 8) | (se << 5) | (sh << 4) | cu;
+}
+
+// The SIMD (0..3) of its CU that a wave runs on: HW_REG_HW_ID bits 5:4, in the GFX9 layout whose CU, SH and SE fields
+// cu_key() uses.
+__device__ __forceinline__ uint32_t simd_id() {
+  uint32_t hwid;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+  return (hwid >> 4) & 0x3;
 }
 
 // The XCC (0..7) a wave runs on: the owner of the L2 it reads and writes through.

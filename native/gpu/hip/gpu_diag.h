@@ -90,6 +90,56 @@ extern "C" {
 //    the march is named by its index in the whole buffer, region * region_words + j.
 //  * Infinity Cache (bgc_diag_cache).  Word i of the buffer holds mix32(u32(i) ^ mix32(~seed)); S is
 //    the sum of all its words modulo 2^32.
+//  * Vector ALU (bgc_diag_valu).  Every wave computes the same values; lane l (0..63) of a wave has its own
+//    operands.  Operand word k of (class cls, round r, lane l) is
+//      w(cls, r, k, l) = mix32(seed ^ mix32(cls << 24 | r << 16 | k << 8 | l)),   w_k for short.
+//    Floating-point operands keep the hash's sign and all of its significand bits and bound the exponent:
+//      f32(h)  = bits (h & 0x807fffff) | (127 + BGC_VALU_F32_EMIN + ((h >> 23) & 15)) << 23:  |x| in [2^-8, 2^8);
+//      f16(h)  = of the low 16 bits of h, (h & 0x83ff) | (15 + BGC_VALU_F16_EMIN + ((h >> 10) & 7)) << 10:  |x| in
+//                [2^-4, 2^4);  f16x2(h) = f16(h & 0xffff) | f16(h >> 16) << 16;
+//      f64(hi, lo) = bits (hi & 0x800fffff) << 32 | (1023 + BGC_VALU_F32_EMIN + ((hi >> 20) & 15)) << 52 | lo.
+//    With these ranges no operand and no correctly rounded result is a NaN, an infinity or a denormal, so the
+//    verdict does not depend on the denormal mode.  fp32 and fp64: a product lies in [2^-16, 2^16) and a sum of a
+//    product and an operand below 2^17; the operands are multiples of 2^-31 (2^-60) and their products of 2^-62
+//    (2^-120), so a sum or difference that is not 0 is at least that, far above the smallest normal number 2^-126
+//    (2^-1022); an exact 0 is allowed.  fp16: the operands are multiples of 2^-14, the smallest normal half, so a
+//    sum that is not 0 is a normal number below 2^5; a product lies in [2^-8, 2^8); the FMA's addend takes the
+//    sign of the product, so |a b + c| lies in [2^-4, 2^9), below the largest half 65504.  a b is a multiple of
+//    2^-28 below 2^8 and c of 2^-14 below 2^4, so a b + c takes at most 37 bits and the host's double arithmetic
+//    is exact: rounding it once to a half (to nearest even) is the fused result.  Conversions: f32 -> i32 takes
+//    |x| < 2^8; f32 -> f16 and bf16 take |x| in [2^-8, 2^8), normal in both formats.
+//    A round of a class produces these 32-bit result words, in this order (40 in all; BGC_VALU_ROUND_WORDS):
+//      int32 (13), a = w_0, b = w_1, c = w_2, all modulo 2^32:  a + b;  a - b;  a b;  (a b) >> 32;
+//        (a mod 2^24)(b mod 2^24) + c;  a << (c & 31);  a >> (c & 31);  a >> (c & 31) arithmetically;
+//        (a >> (c & 31)) & (2^((c >> 8) & 31) - 1);  the bytes of the 64-bit a:b (b the low half) that the four
+//        bytes of c & 0x07070707 select, byte i of the result by byte i of the selector;  (a:b >> (c & 31)) mod 2^32;
+//        the number of 1 bits of a;  the number of leading 0 bits of a (32 for 0).
+//      fp32 (6), x_k = f32(w_k):  fma(x_0, x_1, x_2);  fma(x_3, x_5, x_1) and fma(x_4, x_0, x_2) as one packed
+//        FMA;  p = x_3 x_4;  p + x_5 (two roundings);  x_0 - x_4.
+//      fp16 (3), packed halves A = f16x2(w_0), B = f16x2(w_1), C = (f16x2(w_2) & 0x7fff7fff) | ((A ^ B) &
+//        0x80008000):  fma(A, B, C);  A + B;  A B, each on both halves, the low half in the low 16 bits.
+//      fp64 (6), x_k = f64(w_2k, w_2k+1):  fma(x_0, x_1, x_2);  x_0 + x_1;  x_0 x_1, each as its low word, then
+//        its high word.
+//      cvt (5):  f32(w_0) to i32, truncated;  w_1 as an i32 to f32;  f32(w_2) to f16, zero-extended;  f16(w_3) to
+//        f32;  bf16 of f32(w_4) | bf16 of f32(w_5) << 16.  All to nearest even where they round.
+//      dot (2), a = w_0, b = w_1:  the sum of the four products of the signed bytes of a and b, plus w_2 >> 8
+//        arithmetically;  the same of the unsigned bytes, plus w_2 >> 8.
+//      trans (5):  2^x of x = f32 bits (w_0 & 0x807fffff) | (125 + ((w_0 >> 23) & 7)) << 23;  log2 of the positive
+//        x with the significand of w_1 and exponent t - 5 for t = (w_1 >> 23) & 7 below 4, else t - 3 (so x lies
+//        outside (0.5, 2) and |log2 x| >= 1);  1 / f32(w_2);  1 / sqrt|f32(w_3)|;  sqrt|f32(w_4)|.
+//    Digest: d(cls, l) starts at 0x9e3779b9 + cls, and every result word v, round after round, is folded as
+//    d = mix32(d ^ v).  mix32 is a bijection, so one changed word always changes the final digest.  The six
+//    classes before trans are exact: every result is an integer or an IEEE result rounded to nearest even, and
+//    the host compares all digests with its own.  The transcendental instructions are not bit-specified: their
+//    digests are judged by consensus of the waves, and the raw results of one wave that holds the consensus
+//    against double-precision libm, within BGC_VALU_*_ULPS units in the last place of the fp32 result.
+//    Rate phase: 8 chains per lane, `rate_iters` iterations.  fp32 (chains of 2 packed components), fp16 (2
+//    packed halves) and fp64 (1): x = fma(x, -1, 2047) from x = 1 + l + 64 k for component k = 2 chain + j (fp64:
+//    k = chain), so x alternates between two integers below 2^11, exact in all three formats.  int32: x =
+//    (x mod 2^24) * 0x5bd1e9 + 0x9e3779b9 from x = mix32(seed ^ (chain << 8 | l)).  trans: x = 2^x * 0.5 from
+//    x = 0.25 + (l + 64 chain) / 1024, which settles at 1.  The end digest of a lane starts at 0x85ebca6b + rate
+//    class and folds chain 0's words, then chain 1's, ... (fp32: component 0, component 1; fp16: one packed word;
+//    fp64: low, high); the host computes it for the four exact classes and takes the waves' consensus for trans.
 
 typedef struct {
   uint64_t bytes;          // buffer size tested
@@ -331,6 +381,67 @@ typedef struct {
 //    sum with every sweep's reads coming from another XCD than the last, and checked again.
 int bgc_diag_cache(int device, int rounds, uint32_t region_bytes, int l2_sweeps, uint64_t ic_bytes, int ic_sweeps,
                    uint32_t seed, bgc_cache_result* out);
+// The vector ALU's instruction classes, in the order of every [7] below and of a plant's `cls`.
+#define BGC_VALU_INT32 0  // add, sub, v_mul_lo_u32, v_mul_hi_u32, 24-bit mad, shifts, v_bfe_u32, v_perm_b32, v_alignbit_b32, bit counts
+#define BGC_VALU_FP32 1   // v_fma_f32 (issued in its v_fmac_f32 form), v_pk_fma_f32, v_mul_f32, v_add_f32, v_sub_f32
+#define BGC_VALU_FP16 2   // v_pk_fma_f16, v_pk_add_f16, v_pk_mul_f16
+#define BGC_VALU_FP64 3   // v_fma_f64 (issued in its v_fmac_f64 form), v_add_f64, v_mul_f64
+#define BGC_VALU_CVT 4    // v_cvt_i32_f32, v_cvt_f32_i32, v_cvt_f16_f32, v_cvt_f32_f16, v_cvt_pk_bf16_f32
+#define BGC_VALU_DOT 5    // v_dot4c_i32_i8, v_dot4_u32_u8
+#define BGC_VALU_TRANS 6  // v_exp_f32, v_log_f32, v_rcp_f32, v_rsq_f32, v_sqrt_f32
+#define BGC_VALU_CLASSES 7
+#define BGC_VALU_ROUND_WORDS 40  // 32-bit result words of a lane per round: 13 + 6 + 3 + 6 + 5 + 2 + 5
+// The rate phase's classes, in the order of every [5] below.
+#define BGC_VALU_RATE_FP32 0   // v_pk_fma_f32, TFLOP/s (an FMA counts 2)
+#define BGC_VALU_RATE_FP16 1   // v_pk_fma_f16, TFLOP/s
+#define BGC_VALU_RATE_FP64 2   // v_fma_f64, TFLOP/s
+#define BGC_VALU_RATE_INT32 3  // v_mad_u32_u24, TOP/s (a mad counts 2)
+#define BGC_VALU_RATE_TRANS 4  // v_exp_f32, T instructions/s
+#define BGC_VALU_RATE_CLASSES 5
+// Smallest exponent of the fp32 / fp64 and of the fp16 operands; each range spans 16 (8) binades (derived above).
+#define BGC_VALU_F32_EMIN (-8)
+#define BGC_VALU_F16_EMIN (-4)
+// Accuracy bounds of the transcendental instructions against double-precision libm, in units of the last place of the
+// fp32 result: the largest error measured on the MI355X over seed 0x5eed and 16 other seeds at 64 rounds (69632 values
+// per instruction; profiles/valu_diag/trans_ulps.json), rounded up to a whole unit, plus 1 for the host libm's own error.
+#define BGC_VALU_EXP_ULPS 2.0   // v_exp_f32: measured 0.767
+#define BGC_VALU_LOG_ULPS 2.0   // v_log_f32: measured 0.997
+#define BGC_VALU_RCP_ULPS 2.0   // v_rcp_f32: measured 0.867
+#define BGC_VALU_RSQ_ULPS 2.0   // v_rsq_f32: measured 0.821
+#define BGC_VALU_SQRT_ULPS 2.0  // v_sqrt_f32: measured 0.906
+typedef struct {
+  int cus;                     // CUs of the device
+  int cus_seen;                // distinct CUs that ran a check wave
+  int simds_seen;              // distinct (CU, SIMD) that ran one
+  uint64_t values_checked;     // result words folded into digests: waves * 64 * rounds * BGC_VALU_ROUND_WORDS
+  uint64_t mismatches[7];      // (wave, lane) digests that differ from the host's (trans: from the consensus), by class
+  int consensus_ok;            // more than half of the waves hold the same 64 trans digests
+  uint64_t trans_out_of_bound; // raw trans results of one consensus wave beyond BGC_VALU_*_ULPS of libm
+  int bad_cus;                 // CUs with >= 1 mismatch
+  int bad_simds;               // (CU, SIMD) with >= 1 mismatch
+  int first_bad_cu_key;        // the mismatch with the lowest (CU key, SIMD, wave, class, lane); each -1 if none
+  int first_bad_simd;          // 0..3
+  int first_bad_lane;
+  int first_bad_class;
+  uint64_t bad_lanes;          // bit l: lane l mismatched in some wave
+  double rate[5];              // each rate class's launch: TFLOP/s, TOP/s or T instructions/s
+  double rate_ms[5];           // device time of that launch
+  int rate_ok;                 // every lane's end digest of every rate launch matched
+  int slowest_cu_key;          // CU whose rate waves took longest in the mean over the five launches, -1 if none ran
+  double cu_balance;           // fastest / slowest CU mean wave time (1.0 = balanced)
+  double elapsed_ms;           // the check launch and the five timed launches
+  int bad_cu_keys[64];
+} bgc_valu_result;
+
+// The vector ALU, which does every softmax, normalisation, activation, conversion and optimizer step and which
+// referees every other check here: cus * `waves_per_simd` (1..8) workgroups of four waves, normally one per SIMD
+// of a CU, each run `rounds` (1..64) rounds of a fixed sequence of integer, fp32, fp16, fp64, conversion, integer
+// dot and transcendental instructions on per-lane operands and write one digest per lane and class with the CU
+// and SIMD they ran on.  The device compares nothing: the host recomputes the exact classes and judges the
+// transcendentals by consensus and against libm.  Then one timed launch per rate class, `rate_iters`
+// (1..65536) iterations of 8 chains per lane.  Not covered: the scalar ALU, the floating-point dot products
+// (their internal rounding is unspecified), fp8 conversions and the register file as a memory.
+int bgc_diag_valu(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed, bgc_valu_result* out);
 // ---------------------------------------------------------------------------------------------
 // Planted variants: FOR TESTS ONLY.  Each runs the same implementation as the entry point it is
 // named after, with a list of deliberately wrong values ("plants") written into the diagnostic's
@@ -508,6 +619,30 @@ typedef struct {
 int bgc_diag_cache_delayed(int device, int rounds, uint32_t region_bytes, int l2_sweeps, uint64_t ic_bytes, int ic_sweeps,
                            uint32_t seed, const bgc_cache_delay_plant* delays, int n, bgc_cache_result* out);
 
+// Result word `op` (below the class's count) of `lane` in round `round` of class `cls` ^= xor_mask before it is
+// folded, in check wave `wave` (global wave index: workgroup * 4 + wave of the workgroup) or in every wave
+// (BGC_PLANT_ALL_WAVES).  round < rounds, a non-zero mask, wave below the launch's cus * waves_per_simd * 4.
+typedef struct {
+  int wave, cls, round, lane, op;
+  uint32_t xor_mask;
+} bgc_valu_plant;
+// The first word of chain `chain` (0..7) of `lane` ^= xor_mask after the loop of rate class `cls`'s timed launch.
+typedef struct {
+  int wave, cls, lane, chain;
+  uint32_t xor_mask;
+} bgc_valu_rate_plant;
+int bgc_diag_valu_planted(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed, const bgc_valu_plant* check,
+                          int n_check, const bgc_valu_rate_plant* rate, int n_rate, bgc_valu_result* out);
+// Wave `wave` (or every one) of rate class `cls`'s timed launch waits `ticks` (1..BGC_DIAG_MAX_DELAY_TICKS) of the
+// constant clock after its loop and before it reads its end time.  No value is touched: the time shows in rate,
+// rate_ms, slowest_cu_key and cu_balance only.
+typedef struct {
+  int wave, cls;
+  uint32_t ticks;
+} bgc_valu_delay_plant;
+int bgc_diag_valu_delayed(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed, const bgc_valu_delay_plant* delays,
+                          int n, bgc_valu_result* out);
+
 // ---------------------------------------------------------------------------------------------
 // Generated data: FOR TESTS ONLY, never loaded by the node agent or the diag worker.  Each runs
 // the same implementation as the entry point it is named after and then copies the data that
@@ -570,6 +705,25 @@ int bgc_diag_lds_data(int device, uint32_t seed, int wg, int pass, int grid, voi
 int bgc_diag_cache_data(int device, int rounds, uint32_t region_bytes, int passes, int l2_sweeps, uint64_t ic_bytes,
                         int ic_sweeps, uint32_t seed, void* l2_data, uint64_t l2_capacity, void* ic_data,
                         bgc_cache_result* out);
+
+// What one check wave produced, or what the host referee expects of every wave.
+typedef struct {
+  int cu_key, simd;                      // where the wave ran in the check launch; -1 in the host's expectation
+  int rate_cu_key[BGC_VALU_RATE_CLASSES];  // the CU it ran on in each rate class's timed launch; -1 likewise
+  uint32_t digests[BGC_VALU_CLASSES][64];  // [class][lane]
+  uint32_t raw[64 * BGC_VALU_ROUND_WORDS * 64];  // [round][word][lane], the classes' words in class order; `rounds` rounds
+} bgc_valu_wave;
+// bgc_diag_valu with the plants of bgc_diag_valu_planted and the delays of bgc_diag_valu_delayed (any list may be empty),
+// then wave `wave` (below the launch's wave count, refused once the CU count is known): where it ran, in the check launch
+// and in every timed rate launch of this very run, since the dispatcher places a wave anew in every launch; its digests as
+// it wrote them; and every result word as it folded it, plants applied.  So a test can compare the place that a planted or
+// delayed run names with the place of the wave it planted.
+int bgc_diag_valu_data(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed, int wave, const bgc_valu_plant* check,
+                       int n_check, const bgc_valu_rate_plant* rate, int n_rate, const bgc_valu_delay_plant* delays, int n_delay,
+                       bgc_valu_wave* data, bgc_valu_result* out);
+// The host referee's values for (seed, rounds): the digests it compares with, and every result word (trans: double
+// libm rounded to float, which no digest is compared with).  Touches no device.
+int bgc_diag_valu_expected(uint32_t seed, int rounds, bgc_valu_wave* data);
 
 // PCI bus id of a HIP device ("0000:05:00.0", lower-case hex) — the key the node agent and
 // the RCCL probe use to match a HIP device (renumbered inside a container) to amdsmi.

@@ -8,6 +8,8 @@
 //  * lds.hip: the per-CU march test of the whole Local Data Share and its read rate;
 //  * cache.hip: the per-XCC march through every XCD's L2 with its read rate, and the Infinity Cache's
 //    pattern check and read rate;
+//  * valu.hip: the per-SIMD vector-ALU check (integer, fp32, fp16, fp64, conversions, integer dots and
+//    transcendentals, refereed by the host through valu_ref.h) and the vector rates;
 //  * gemm_soak.hip: the ABFT-checked LDS-tiled GEMMs (gemm_soak and the 8-phase gemm_pingpong).
 // The design notes in those files follow the CDNA4 guides (cdna_hip_programming.md,
 // MI355X_MICROARCH.md).

@@ -257,6 +257,9 @@ void register_gpu(py::module_& m) {
     return dump_nogil([&] { return Diag::instance().cache(device, rounds, region_bytes, l2_sweeps, ic_bytes, ic_sweeps, seed); });
   }, py::arg("device"), py::arg("rounds") = 4, py::arg("region_bytes") = BGC_L2_REGION_BYTES, py::arg("l2_sweeps") = 4096,
      py::arg("ic_bytes") = 128ULL << 20, py::arg("ic_sweeps") = 128, py::arg("seed") = 0x5eed);
+  m.def("diag_valu", [](int device, int waves_per_simd, int rounds, int rate_iters, unsigned seed) {
+    return dump_nogil([&] { return Diag::instance().valu(device, waves_per_simd, rounds, rate_iters, seed); });
+  }, py::arg("device"), py::arg("waves_per_simd") = 2, py::arg("rounds") = 16, py::arg("rate_iters") = 16384, py::arg("seed") = 0x5eed);
   m.def("diag_gemm", [](int device, int mm, int nn, int kk, const std::string& a, const std::string& b) {
     if (a.size() != static_cast<size_t>(mm) * kk * 2 || b.size() != static_cast<size_t>(kk) * nn * 2) {
       throw std::invalid_argument("A must be M*K and B K*N bf16 values");
@@ -390,6 +393,25 @@ void register_gpu(py::module_& m) {
                    seed, d.data(), count(d));
   }, py::arg("device"), py::arg("rounds"), py::arg("region_bytes"), py::arg("l2_sweeps"), py::arg("ic_bytes"), py::arg("ic_sweeps"),
      py::arg("seed"), py::arg("delays"));
+  // check plants (wave or -1, class, round, lane, result word, mask) and rate plants (wave or -1, rate class, lane, chain, mask)
+  m.def("diag_valu_planted", [](int device, int waves_per_simd, int rounds, int rate_iters, unsigned seed,
+                                const std::vector<std::tuple<int, int, int, int, int, unsigned>>& check_plants,
+                                const std::vector<std::tuple<int, int, int, int, unsigned>>& rate_plants) {
+    std::vector<bgc_valu_plant> c;
+    std::vector<bgc_valu_rate_plant> r;
+    for (const auto& [wave, cls, round, lane, op, mask] : check_plants) c.push_back({wave, cls, round, lane, op, mask});
+    for (const auto& [wave, cls, lane, chain, mask] : rate_plants) r.push_back({wave, cls, lane, chain, mask});
+    return planted("valu diag", BGC_DIAG_ENTRY(bgc_diag_valu_planted), device, waves_per_simd, rounds, rate_iters, seed, c.data(), count(c),
+                   r.data(), count(r));
+  }, py::arg("device"), py::arg("waves_per_simd"), py::arg("rounds"), py::arg("rate_iters"), py::arg("seed"), py::arg("check_plants"),
+     py::arg("rate_plants"));
+  // (wave or -1, rate class, ticks of the constant clock) in that class's timed rate launch
+  m.def("diag_valu_delayed", [](int device, int waves_per_simd, int rounds, int rate_iters, unsigned seed,
+                                const std::vector<std::tuple<int, int, unsigned>>& delays) {
+    std::vector<bgc_valu_delay_plant> d;
+    for (const auto& [wave, cls, ticks] : delays) d.push_back({wave, cls, ticks});
+    return planted("valu diag", BGC_DIAG_ENTRY(bgc_diag_valu_delayed), device, waves_per_simd, rounds, rate_iters, seed, d.data(), count(d));
+  }, py::arg("device"), py::arg("waves_per_simd"), py::arg("rounds"), py::arg("rate_iters"), py::arg("seed"), py::arg("delays"));
   // Delay plants: (wave or -1, ticks of the constant clock) in the timed throughput launch; and a burn
   // whose launches from `first_delayed_launch` on have every wave delayed by `ticks`.
   m.def("diag_mfma_delayed", [](int device, int waves_per_cu, int iters, unsigned seed,
@@ -511,6 +533,31 @@ void register_gpu(py::module_& m) {
     return py::make_tuple(v.dump(), py::bytes(l2), py::bytes(ic));
   }, py::arg("device"), py::arg("rounds"), py::arg("region_bytes"), py::arg("passes"), py::arg("l2_sweeps"), py::arg("ic_bytes"),
      py::arg("ic_sweeps"), py::arg("seed"));
+  // the result and one check wave as bytes of bgc_valu_wave; and the host referee's expectation alike, without a device
+  m.def("diag_valu_data", [](int device, int waves_per_simd, int rounds, int rate_iters, unsigned seed, int wave,
+                             const std::vector<std::tuple<int, int, int, int, int, unsigned>>& check_plants,
+                             const std::vector<std::tuple<int, int, int, int, unsigned>>& rate_plants,
+                             const std::vector<std::tuple<int, int, unsigned>>& delays) {
+    std::vector<bgc_valu_plant> c;
+    std::vector<bgc_valu_rate_plant> r;
+    std::vector<bgc_valu_delay_plant> d;
+    for (const auto& [w, cls, round, lane, op, mask] : check_plants) c.push_back({w, cls, round, lane, op, mask});
+    for (const auto& [w, cls, lane, chain, mask] : rate_plants) r.push_back({w, cls, lane, chain, mask});
+    for (const auto& [w, cls, ticks] : delays) d.push_back({w, cls, ticks});
+    std::string data(sizeof(bgc_valu_wave), '\0');
+    const std::string result = planted("valu diag", BGC_DIAG_ENTRY(bgc_diag_valu_data), device, waves_per_simd, rounds, rate_iters, seed, wave,
+                                       c.data(), count(c), r.data(), count(r), d.data(), count(d), reinterpret_cast<bgc_valu_wave*>(data.data()));
+    return py::make_tuple(result, py::bytes(data));
+  }, py::arg("device"), py::arg("waves_per_simd"), py::arg("rounds"), py::arg("rate_iters"), py::arg("seed"), py::arg("wave"),
+     py::arg("check_plants"), py::arg("rate_plants"), py::arg("delays"));
+  m.def("diag_valu_expected", [](unsigned seed, int rounds) {
+    std::string data(sizeof(bgc_valu_wave), '\0');
+    Diag::instance().check("valu diag", BGC_DIAG_ENTRY(bgc_diag_valu_expected)(seed, rounds, reinterpret_cast<bgc_valu_wave*>(data.data())));
+    return py::bytes(data);
+  }, py::arg("seed"), py::arg("rounds"));
+  m.def("diag_valu_trans_ulps", [] {
+    return py::make_tuple(BGC_VALU_EXP_ULPS, BGC_VALU_LOG_ULPS, BGC_VALU_RCP_ULPS, BGC_VALU_RSQ_ULPS, BGC_VALU_SQRT_ULPS);
+  });
 #undef BGC_DIAG_ENTRY
   m.def("pcie_check", [](std::shared_ptr<PyBackend> b, int index, int hip_device, unsigned long long bytes, unsigned seed) {
     return dump_nogil([&] {
