@@ -101,10 +101,6 @@ struct MarchBin {
   unsigned long long checked, bad;
   unsigned bits, first;
 };
-struct RateBin {
-  unsigned long long ticks;
-  unsigned wgs, pad;
-};
 struct IcBin {
   unsigned long long bad;
   unsigned bits, first;
@@ -113,14 +109,8 @@ struct IcBin {
 // Test plants (gpu_diag.h).  l2_march and l2_rate end in a pack `Extras... extras`: empty in the
 // production instantiations, which call the empty overloads below, a plant list behind
 // bgc_diag_cache_planted (march) or bgc_diag_cache_delayed (rate).
-struct L2Plants {  // in device memory
-  const bgc_l2_plant* p = nullptr;
-  int n = 0;
-};
-struct DelayPlants {
-  const bgc_cache_delay_plant* p = nullptr;
-  int n = 0;
-};
+using L2Plants = PlantList<bgc_l2_plant>;
+using DelayPlants = PlantList<bgc_cache_delay_plant>;
 
 // The barrier behind a fill.  A workgroup barrier alone does not wait for the stores of its own wave
 // (one CU's vector memory operations stay in order anyway): with the wait, every store of the fill
@@ -256,7 +246,7 @@ __global__ __launch_bounds__(kThreads) void l2_rate(uint32_t* buf, uint32_t regi
   if (t == 0) {
     RateBin* bin = &bins[xcc_id()];
     atomicAdd(&bin->ticks, static_cast<unsigned long long>(t1 - t0));
-    atomicAdd(&bin->wgs, 1u);
+    atomicAdd(&bin->n, 1u);
   }
 }
 
@@ -361,15 +351,6 @@ bool extras_ok(const CacheArgs& a, const CacheExtras& x) {
   return l2_ok && ic_ok && delays_ok && data_ok;
 }
 
-// a plant list in device memory (nothing for an empty one)
-template <class P>
-int upload(DeviceBuffer& d, const P* plants, int n) {
-  if (n == 0) return 0;
-  HIP_TRY(d.alloc(static_cast<size_t>(n) * sizeof(P)));
-  HIP_TRY(hipMemcpy(d.p, plants, static_cast<size_t>(n) * sizeof(P), hipMemcpyHostToDevice));
-  return 0;
-}
-
 template <class... Extras>
 void launch_march(int grid, uint32_t* buf, uint32_t region_words, uint32_t seed, int round, int passes, MarchBin* bins, Extras... extras) {
   hipLaunchKernelGGL((l2_march<Extras...>), dim3(grid), dim3(kBlock), 0, nullptr, buf, region_words, seed, round, passes, bins, extras...);
@@ -399,9 +380,7 @@ int ic_run(int cus, const CacheArgs& a, const CacheExtras& x, const Events& ev, 
   DeviceBuffer buf, sums, bin;
   HIP_TRY(buf.alloc(a.ic_bytes));
   HIP_TRY(sums.alloc(2 * sizeof(unsigned), true));  // S of the fill, the sweeps' total
-  const IcBin init{0, 0, ~0u};
-  HIP_TRY(bin.alloc(sizeof(IcBin)));
-  HIP_TRY(hipMemcpy(bin.p, &init, sizeof(init), hipMemcpyHostToDevice));
+  HIP_TRY(bin.alloc_filled(1, IcBin{0, 0, ~0u}));
   auto check = [&] { hipLaunchKernelGGL(ic_check, dim3(grid), dim3(kBlock), 0, nullptr, buf.as<const u32x4>(), n_elems, s, bin.as<IcBin>()); };
   float ms_fill = 0.f, ms_check = 0.f, ms_rate = 0.f, ms_again = 0.f;
   if (timed(ev, &ms_fill, [&] {
@@ -424,7 +403,7 @@ int ic_run(int cus, const CacheArgs& a, const CacheExtras& x, const Events& ev, 
   out->ic_mismatches = h_bin.bad;
   if (h_bin.bad) out->ic_first_bad_word = h_bin.first;
   out->ic_bad_bits = h_bin.bits;
-  out->ic_read_tbps = ms_rate > 0 ? static_cast<double>(a.ic_bytes) * a.ic_sweeps / (ms_rate * 1e-3) / 1e12 : 0.0;
+  out->ic_read_tbps = tera_per_s(static_cast<double>(a.ic_bytes) * a.ic_sweeps, ms_rate);
   out->ic_rate_ok = h_sums[1] == static_cast<uint32_t>(a.ic_sweeps) * h_sums[0];
   out->elapsed_ms += ms_fill + ms_check + ms_rate + ms_again;
   return 0;
@@ -445,11 +424,8 @@ int cache_run(int device, const CacheArgs& a, const CacheExtras& x, bgc_cache_re
   HIP_TRY(hipSetDevice(device));
   const int cus = cu_count(device), grid = cus;
   out->cus = cus;
-  const bool wg_beyond = std::any_of(x.l2, x.l2 + x.n_l2, [&](const bgc_l2_plant& p) { return p.wg >= grid; }) ||
-                         std::any_of(x.delays, x.delays + x.n_delay, [&](const bgc_cache_delay_plant& p) { return p.wg >= grid; });
-  if (wg_beyond) {
-    g_last_error = "invalid arguments: plant in a workgroup beyond the launch";
-    return 1;
+  if (any_beyond(x.l2, x.n_l2, &bgc_l2_plant::wg, grid) || any_beyond(x.delays, x.n_delay, &bgc_cache_delay_plant::wg, grid)) {
+    return refuse(kWorkgroupBeyond);
   }
   const uint32_t region_words = a.region_bytes / 4;
   const size_t l2_bytes = static_cast<size_t>(grid) * a.region_bytes;
@@ -459,10 +435,8 @@ int cache_run(int device, const CacheArgs& a, const CacheExtras& x, bgc_cache_re
   }
   DeviceBuffer l2, d_plants, d_delays, march_bins, rate_bins, fails;
   HIP_TRY(l2.alloc(l2_bytes));
-  if (upload(d_plants, x.l2, x.n_l2) != 0 || upload(d_delays, x.delays, x.n_delay) != 0) return 1;
-  const std::vector<MarchBin> init(kMaxXccs, MarchBin{0, 0, 0, ~0u});
-  HIP_TRY(march_bins.alloc(kMaxXccs * sizeof(MarchBin)));
-  HIP_TRY(hipMemcpy(march_bins.p, init.data(), kMaxXccs * sizeof(MarchBin), hipMemcpyHostToDevice));
+  if (upload_plants(d_plants, x.l2, x.n_l2) != 0 || upload_plants(d_delays, x.delays, x.n_delay) != 0) return 1;
+  HIP_TRY(march_bins.alloc_filled(kMaxXccs, MarchBin{0, 0, 0, ~0u}));
   HIP_TRY(rate_bins.alloc(kMaxXccs * sizeof(RateBin), true));
   HIP_TRY(fails.alloc(sizeof(unsigned), true));
   Events ev;
@@ -502,11 +476,8 @@ int cache_run(int device, const CacheArgs& a, const CacheExtras& x, bgc_cache_re
   HIP_TRY(hipMemcpy(h_march, march_bins.p, sizeof(h_march), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(h_rate, rate_bins.p, sizeof(h_rate), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(&h_fails, fails.p, sizeof(unsigned), hipMemcpyDeviceToHost));
-  int rate_khz = 0;
-  if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || rate_khz <= 0) {
-    rate_khz = 100000;  // CDNA constant clock: 100 MHz
-  }
-  double fastest = 0, slowest = 0;  // mean loop time of a rate workgroup on an XCC
+  const double ticks_per_us = constant_clock_khz(device) * 1e-3;
+  TimingFold fold;  // of the mean loop time of a rate workgroup on an XCC
   for (int k = 0; k < kMaxXccs; ++k) {
     const MarchBin& m = h_march[k];
     if (m.checked) {
@@ -523,21 +494,12 @@ int cache_run(int device, const CacheArgs& a, const CacheExtras& x, bgc_cache_re
         out->l2_bad_xccs++;
       }
     }
-    const RateBin& r = h_rate[k];
-    out->xcc_wgs[k] = static_cast<int>(r.wgs);
-    if (r.wgs) {
-      const double us = static_cast<double>(r.ticks) / r.wgs / (rate_khz * 1e-3);
-      out->xcc_us[k] = us;
-      fastest = fastest == 0 ? us : std::min(fastest, us);
-      if (us > slowest) {
-        slowest = us;
-        out->slowest_xcc = k;
-      }
-    }
+    out->xcc_wgs[k] = static_cast<int>(h_rate[k].n);
+    out->xcc_us[k] = fold.add(k, h_rate[k].ticks, h_rate[k].n, ticks_per_us);
   }
-  out->xcc_balance = slowest > 0 ? fastest / slowest : 0.0;
-  const double bytes = static_cast<double>(grid) * a.l2_sweeps * a.region_bytes;
-  out->l2_read_tbps = ms_rate > 0 ? bytes / (ms_rate * 1e-3) / 1e12 : 0.0;
+  out->slowest_xcc = fold.slowest_key;
+  out->xcc_balance = fold.balance();
+  out->l2_read_tbps = tera_per_s(static_cast<double>(grid) * a.l2_sweeps * a.region_bytes, ms_rate);
   out->l2_rate_ok = h_fails == 0;
   out->elapsed_ms = ms_march + ms_rate;
   return a.ic_bytes ? ic_run(cus, a, x, ev, out) : 0;

@@ -1,15 +1,40 @@
 // Shared by the diagnostics' sources (gpu_diag.hip, hbm.hip, mfma.hip, lds.hip, cache.hip, valu.hip, gemm_soak.hip): vector
-// types, the hash, the CU a wave runs on, the marches' pattern and wrong-word record, the delay plants' wait, the
-// last-error string and the host helpers every entry point uses.
+// types, the hash, the CU a wave runs on, the marches' pattern and wrong-word record, the delay plants' wait, a rate
+// launch's timing bin, the last-error string and the host helpers every entry point uses: device buffers and events,
+// the test plants' list, upload and beyond-the-launch refusal, the constant clock's rate, the rate formula and
+// (diag_fold.h) the fold of the timing bins.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 #include <type_traits>
 #include <vector>
 
+#include "diag_fold.h"
 #include "gpu_diag.h"
+
+// The two types that kernels of several sources take as arguments.  They are in the unnamed namespace, where every
+// source has its kernels: a kernel's symbol names its argument types, and so stays what it is whichever file
+// declares them.
+namespace {
+
+// A rate launch's timing bin of one key (a CU: cu_key(), or an XCC: xcc_id()): the ticks of the constant clock that
+// the `n` workgroups or waves that ran there took in all.  TimingFold (diag_fold.h) folds the bins.
+struct RateBin {
+  unsigned long long ticks;
+  unsigned n, pad;
+};
+
+// Test plants (gpu_diag.h, "planted variants") in device memory.  The planted instantiation of a kernel takes one.
+template <class P>
+struct PlantList {
+  const P* p = nullptr;
+  int n = 0;
+};
+
+}  // namespace
 
 namespace bgc_diag __attribute__((visibility("hidden"))) {
 
@@ -117,6 +142,13 @@ struct DeviceBuffer {
     const hipError_t e = hipMalloc(&p, bytes);
     return e == hipSuccess && zero ? hipMemset(p, 0, bytes) : e;
   }
+  // `n` copies of `init`: bins whose `first` starts at ~0
+  template <class T>
+  hipError_t alloc_filled(size_t n, const T& init) {
+    const std::vector<T> host(n, init);
+    const hipError_t e = alloc(n * sizeof(T));
+    return e == hipSuccess ? hipMemcpy(p, host.data(), n * sizeof(T), hipMemcpyHostToDevice) : e;
+  }
   template <class T>
   T* as() const {
     return static_cast<T*>(p);
@@ -166,6 +198,38 @@ void note_bad_cu(Result* out, int key) {
 inline bool plant_list_ok(const void* plants, int n) {
   return n >= 0 && n <= BGC_DIAG_MAX_PLANTS && (n == 0 || plants);
 }
+
+// A plant list in device memory (nothing for an empty one).
+template <class P>
+int upload_plants(DeviceBuffer& d, const P* plants, int n) {
+  if (n == 0) return 0;
+  HIP_TRY(d.alloc(static_cast<size_t>(n) * sizeof(P)));
+  HIP_TRY(hipMemcpy(d.p, plants, static_cast<size_t>(n) * sizeof(P), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// Whether a plant names a wave or a workgroup (its member `place`) that a launch of `limit` of them does not have;
+// the caller then refuses, once the launch size is known, with one of the two texts.
+constexpr const char* kWaveBeyond = "invalid arguments: plant in a wave beyond the launch";
+constexpr const char* kWorkgroupBeyond = "invalid arguments: plant in a workgroup beyond the launch";
+template <class P>
+bool any_beyond(const P* plants, size_t n, int P::*place, int limit) {
+  return std::any_of(plants, plants + n, [&](const P& p) { return p.*place >= limit; });
+}
+inline int refuse(const char* why) {
+  g_last_error = why;
+  return 1;
+}
+
+// kHz of the constant clock that wall_clock64() reads
+inline int constant_clock_khz(int device) {
+  int khz = 0;
+  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || khz <= 0) khz = 100000;  // CDNA: 100 MHz
+  return khz;
+}
+
+// 1e12 operations or bytes per second: `x` of them in `ms`
+inline double tera_per_s(double x, float ms) { return ms > 0 ? x / (ms * 1e-3) / 1e12 : 0.0; }
 
 // *p = f(*p) on one value in device memory: a host read-modify-write on the null stream, so it is
 // ordered after the null-stream kernels that produced the data and before those that check it.

@@ -63,7 +63,7 @@ __device__ __forceinline__ void slab_stream(const u32x4* src, uint64_t n16, Cons
 }
 
 // a lane's wrong words and the lowest of them
-struct BadWords {
+struct BadCount {
   unsigned long long count = 0, first = ~0ULL;
   __device__ __forceinline__ void add(unsigned long long n, unsigned long long where) {
     count += n;
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(kBlock) void hbm_copy(const u32x4* __restrict__ src
 __global__ __launch_bounds__(kBlock) void hbm_check(const u32x4* __restrict__ buf, uint64_t n16, uint32_t seed,
                                                     unsigned long long* __restrict__ bad,
                                                     unsigned long long* __restrict__ first_bad) {
-  BadWords w;
+  BadCount w;
   slab_stream<true>(buf, n16, [=, &w](uint64_t i, const u32x4& v) {
     const u32x4 e = pattern16(i, seed);
     const int nb = (v.x != e.x) + (v.y != e.y) + (v.z != e.z) + (v.w != e.w);
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(kBlock) void walk_fill(u32x4* __restrict__ buf, uin
 __global__ __launch_bounds__(kBlock) void walk_check(const u32x4* __restrict__ buf, uint64_t n16, uint64_t key,
                                                      unsigned long long* __restrict__ bad,
                                                      unsigned long long* __restrict__ first_bad_addr) {
-  BadWords w;
+  BadCount w;
   slab_stream<true>(buf, n16, [=, &w](uint64_t i, const u32x4& v) {
     const u32x4 e = walk_value(&buf[i], key);
     const bool b0 = v.x != e.x || v.y != e.y, b1 = v.z != e.z || v.w != e.w;
@@ -156,12 +156,10 @@ struct Chunks {  // the HBM walk's allocations, freed on every exit path
   }
 };
 
-// {bad words, first bad} counters of the check kernels
-int reset_counters(unsigned long long* bad) {
-  const unsigned long long init[2] = {0ULL, ~0ULL};
-  HIP_TRY(hipMemcpy(bad, init, sizeof(init), hipMemcpyHostToDevice));
-  return 0;
-}
+// {bad words, first bad} counters of the check kernels, as they start
+struct Counters {
+  unsigned long long bad = 0, first = ~0ULL;
+};
 
 uint64_t mix64(uint64_t x) {
   x ^= x >> 33;
@@ -189,9 +187,8 @@ int hbm_run(int device, uint64_t bytes, int iters, uint32_t seed, const bgc_hbm_
   DeviceBuffer a, b, counters;
   HIP_TRY(a.alloc(bytes));
   HIP_TRY(b.alloc(bytes));
-  HIP_TRY(counters.alloc(2 * sizeof(unsigned long long)));
+  HIP_TRY(counters.alloc_filled(1, Counters{}));
   auto* bad = counters.as<unsigned long long>();
-  if (reset_counters(bad) != 0) return 1;
   const dim3 grid(cu_count(device) * 8), block(kBlock);
   Events ev;
   HIP_TRY(ev.create());
@@ -303,7 +300,8 @@ int walk_run(int device, double fraction, uint64_t target_bytes, uint64_t chunk_
       break;
     }
     const uint64_t key = pass == 0 ? key0 : ~key0;
-    if (reset_counters(bad) != 0) return 1;
+    const Counters none;
+    HIP_TRY(hipMemcpy(bad, &none, sizeof(none), hipMemcpyHostToDevice));
     float ms = 0.f;
     if (timed(ev, &ms, [&] {
           for (const auto& c : chunks.v) {

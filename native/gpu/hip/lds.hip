@@ -54,19 +54,12 @@ __device__ __forceinline__ uint32_t wg_seed(uint32_t seed, uint32_t wg) { return
 struct MarchBin {
   unsigned checked, bad, bits, first;
 };
-struct RateBin {
-  unsigned long long ticks;
-  unsigned wgs, pad;
-};
 
 // Test plants and the generated-data copy (gpu_diag.h).  lds_march ends in a pack `Extras... extras`:
 // empty in the production instantiation, which calls the empty overloads below (neither a plant nor
 // the barrier that follows it), a plant list behind bgc_diag_lds_planted, a dump behind
 // bgc_diag_lds_data.
-struct LdsPlants {  // in device memory
-  const bgc_lds_plant* p = nullptr;
-  int n = 0;
-};
+using LdsPlants = PlantList<bgc_lds_plant>;
 struct LdsDump {
   int wg, pass;
   u32x4* out;  // kElems elements
@@ -184,7 +177,7 @@ __global__ __launch_bounds__(kThreads) void lds_rate(uint32_t seed, int iters, R
   if (sum != static_cast<uint32_t>(iters) * sweep) atomicAdd(fails, 1u);
   if (t == 0) {
     atomicAdd(&bins[key].ticks, static_cast<unsigned long long>(t1 - t0));
-    atomicAdd(&bins[key].wgs, 1u);
+    atomicAdd(&bins[key].n, 1u);
   }
 }
 
@@ -198,12 +191,7 @@ void launch_rate(int grid, uint32_t seed, int iters, RateBin* bins, unsigned* fa
 }
 
 // the march's bins on the device, every `first` at ~0
-int alloc_march_bins(DeviceBuffer& bins) {
-  const std::vector<MarchBin> init(BGC_DIAG_MAX_CU_KEYS, MarchBin{0, 0, 0, ~0u});
-  HIP_TRY(bins.alloc(init.size() * sizeof(MarchBin)));
-  HIP_TRY(hipMemcpy(bins.p, init.data(), init.size() * sizeof(MarchBin), hipMemcpyHostToDevice));
-  return 0;
-}
+hipError_t alloc_march_bins(DeviceBuffer& bins) { return bins.alloc_filled(BGC_DIAG_MAX_CU_KEYS, MarchBin{0, 0, 0, ~0u}); }
 
 bool lds_plant_ok(const bgc_lds_plant& p) {
   return p.wg >= BGC_PLANT_ALL_WAVES && (p.pass == 0 || p.pass == 1) && p.word < BGC_LDS_WORDS && p.xor_mask != 0;
@@ -220,18 +208,10 @@ int lds_run(int device, int wgs_per_cu, int rate_iters, uint32_t seed, const bgc
   HIP_TRY(hipSetDevice(device));
   const int cus = cu_count(device), grid = cus * wgs_per_cu;
   out->cus = cus;
-  for (int j = 0; j < n; ++j) {
-    if (plants[j].wg >= grid) {
-      g_last_error = "invalid arguments: plant in a workgroup beyond the launch";
-      return 1;
-    }
-  }
+  if (any_beyond(plants, n, &bgc_lds_plant::wg, grid)) return refuse(kWorkgroupBeyond);
   DeviceBuffer d_plants, march_bins, rate_bins, fails;
-  if (n > 0) {
-    HIP_TRY(d_plants.alloc(static_cast<size_t>(n) * sizeof(bgc_lds_plant)));
-    HIP_TRY(hipMemcpy(d_plants.p, plants, static_cast<size_t>(n) * sizeof(bgc_lds_plant), hipMemcpyHostToDevice));
-  }
-  if (alloc_march_bins(march_bins) != 0) return 1;
+  if (upload_plants(d_plants, plants, n) != 0) return 1;
+  HIP_TRY(alloc_march_bins(march_bins));
   HIP_TRY(rate_bins.alloc(BGC_DIAG_MAX_CU_KEYS * sizeof(RateBin), true));
   HIP_TRY(fails.alloc(sizeof(unsigned), true));
   Events ev;
@@ -257,7 +237,7 @@ int lds_run(int device, int wgs_per_cu, int rate_iters, uint32_t seed, const bgc
   HIP_TRY(hipMemcpy(h_march.data(), march_bins.p, h_march.size() * sizeof(MarchBin), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(h_rate.data(), rate_bins.p, h_rate.size() * sizeof(RateBin), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(&h_fails, fails.p, sizeof(unsigned), hipMemcpyDeviceToHost));
-  double fastest = 0, slowest = 0;  // ticks of one rate workgroup on a CU
+  TimingFold fold;  // of the ticks of one rate workgroup on a CU
   for (int k = 0; k < BGC_DIAG_MAX_CU_KEYS; ++k) {
     const MarchBin& m = h_march[static_cast<size_t>(k)];
     if (m.checked) {
@@ -273,19 +253,11 @@ int lds_run(int device, int wgs_per_cu, int rate_iters, uint32_t seed, const bgc
         note_bad_cu(out, k);
       }
     }
-    const RateBin& r = h_rate[static_cast<size_t>(k)];
-    if (r.wgs) {
-      const double ticks = static_cast<double>(r.ticks) / r.wgs;
-      fastest = fastest == 0 ? ticks : std::min(fastest, ticks);
-      if (ticks > slowest) {
-        slowest = ticks;
-        out->slowest_cu_key = k;
-      }
-    }
+    fold.add(k, h_rate[static_cast<size_t>(k)].ticks, h_rate[static_cast<size_t>(k)].n, 1.0);
   }
-  out->cu_balance = slowest > 0 ? fastest / slowest : 0.0;
-  const double bytes = static_cast<double>(cus) * rate_iters * (4.0 * kWords);
-  out->read_tbps = ms_rate > 0 ? bytes / (ms_rate * 1e-3) / 1e12 : 0.0;
+  out->slowest_cu_key = fold.slowest_key;
+  out->cu_balance = fold.balance();
+  out->read_tbps = tera_per_s(static_cast<double>(cus) * rate_iters * (4.0 * kWords), ms_rate);
   out->rate_ok = h_fails == 0;
   out->elapsed_ms = ms_march + ms_rate;
   return 0;
@@ -311,7 +283,7 @@ int bgc_diag_lds_data(int device, uint32_t seed, int wg, int pass, int grid, voi
   }
   HIP_TRY(hipSetDevice(device));
   DeviceBuffer bins, dump;
-  if (alloc_march_bins(bins) != 0) return 1;
+  HIP_TRY(alloc_march_bins(bins));
   HIP_TRY(dump.alloc(4 * kWords, true));
   launch_march(grid, seed, bins.as<MarchBin>(), LdsDump{wg, pass, dump.as<u32x4>()});
   HIP_TRY(hipGetLastError());

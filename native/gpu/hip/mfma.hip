@@ -252,11 +252,6 @@ using Bf16Tile = DenseTile<Bf16Path, false>;
 // plant list in the instantiations behind the *_planted entry points (wrong values) and the *_delayed
 // ones (DelayPlants: waits on the constant clock).  Everything else, the comparison, the
 // wave reduction and the report, is the same source for both; with_plants() below picks between them.
-template <class P>
-struct PlantList {  // in device memory
-  const P* p = nullptr;
-  int n = 0;
-};
 using CheckPlants = PlantList<bgc_mfma_check_plant>;
 using RatePlants = PlantList<bgc_mfma_rate_plant>;
 using DelayPlants = PlantList<bgc_mfma_delay_plant>;
@@ -579,15 +574,8 @@ struct HostPlants {
   // the device (a launch without plants allocates nothing).
   int upload(int blocks) {
     for (int l = 0; l < 4; ++l) {
-      for (const At& p : host[l]) {
-        if (p.wave >= blocks * (kBlock / 64)) {
-          g_last_error = "invalid arguments: plant in a wave beyond the launch";
-          return 1;
-        }
-      }
-      if (host[l].empty()) continue;
-      HIP_TRY(dev[l].alloc(host[l].size() * sizeof(At)));
-      HIP_TRY(hipMemcpy(dev[l].p, host[l].data(), host[l].size() * sizeof(At), hipMemcpyHostToDevice));
+      if (any_beyond(host[l].data(), host[l].size(), &At::wave, blocks * (kBlock / 64))) return refuse(kWaveBeyond);
+      if (upload_plants(dev[l], host[l].data(), static_cast<int>(host[l].size())) != 0) return 1;
     }
     return 0;
   }
@@ -639,7 +627,6 @@ template <class Tile>
 double rate_flops(int blocks, int iters) {
   return static_cast<double>(blocks) * (kBlock / 64) * iters * 4.0 * (2.0 * 16 * 16 * Tile::kK);
 }
-double tera_per_s(double flops, float ms) { return ms > 0 ? flops / (ms * 1e-3) / 1e12 : 0.0; }
 
 // Per-XCC bins of a timed (kTimed) throughput launch: the waves that ran on each XCC and the sum of their ticks.
 struct XccBins {
@@ -751,19 +738,13 @@ int mfma_run(int device, int waves_per_cu, int throughput_iters, uint32_t seed, 
   unsigned h_waves[8];
   HIP_TRY(hipMemcpy(h_ticks, xcc.ticks.p, sizeof(h_ticks), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(h_waves, xcc.waves.p, sizeof(h_waves), hipMemcpyDeviceToHost));
-  int rate_khz = 0;
-  if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || rate_khz <= 0) {
-    rate_khz = 100000;  // CDNA constant clock: 100 MHz
-  }
-  double lo = 0, hi = 0;
+  const double ticks_per_us = constant_clock_khz(device) * 1e-3;
+  TimingFold fold;  // of a wave's mean loop time on an XCC; the result names no slowest XCC
   for (int x = 0; x < 8; ++x) {
     out->xcc_waves[x] = static_cast<int>(h_waves[x]);
-    out->xcc_wave_us[x] = h_waves[x] ? static_cast<double>(h_ticks[x]) / h_waves[x] / (rate_khz * 1e-3) : 0.0;
-    if (!h_waves[x]) continue;
-    lo = lo == 0 ? out->xcc_wave_us[x] : std::min(lo, out->xcc_wave_us[x]);
-    hi = std::max(hi, out->xcc_wave_us[x]);
+    out->xcc_wave_us[x] = fold.add(x, h_ticks[x], h_waves[x], ticks_per_us);
   }
-  out->xcc_balance = hi > 0 ? lo / hi : 0.0;
+  out->xcc_balance = fold.balance();
   unsigned xcc_mask = 0;
   if (run.bins.fold(out, {&out->mismatches}, &xcc_mask) != 0 || run.throughput_ok(&out->throughput_ok) != 0) return 1;
   out->xccs_seen = __builtin_popcount(xcc_mask);
@@ -868,16 +849,8 @@ struct BurnValuePlants {
   }
   // Once the launch size is known: refuse a plant in a wave beyond it, then copy the plants to the device.
   int upload(int blocks) {
-    for (const bgc_mfma_rate_plant& p : host) {
-      if (p.wave >= blocks * (kBlock / 64)) {
-        g_last_error = "invalid arguments: plant in a wave beyond the launch";
-        return 1;
-      }
-    }
-    if (host.empty()) return 0;
-    HIP_TRY(dev.alloc(host.size() * sizeof(bgc_mfma_rate_plant)));
-    HIP_TRY(hipMemcpy(dev.p, host.data(), host.size() * sizeof(bgc_mfma_rate_plant), hipMemcpyHostToDevice));
-    return 0;
+    if (any_beyond(host.data(), host.size(), &bgc_mfma_rate_plant::wave, blocks * (kBlock / 64))) return refuse(kWaveBeyond);
+    return upload_plants(dev, host.data(), static_cast<int>(host.size()));
   }
   RatePlants of(int l) const {
     const auto [lo, hi] = std::equal_range(launch.begin(), launch.end(), l);

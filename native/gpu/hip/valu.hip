@@ -212,11 +212,6 @@ struct Chain<BGC_VALU_RATE_TRANS> {
   __device__ static T flip(T x, uint32_t mask) { return ref::f32_of(ref::bits_of(x) ^ mask); }
 };
 
-struct RateBin {
-  unsigned long long ticks;
-  unsigned waves, pad;
-};
-
 // after the loop: the value plants, where the dumped wave runs, then the wait for the largest `ticks` that names this wave
 template <class C>
 __device__ __forceinline__ void after_loop(typename C::T* x, int cls, int wave, int lane, const RateExtras& e, C) {
@@ -282,7 +277,7 @@ __global__ __launch_bounds__(kBlock) void valu_rate(uint32_t seed, int iters, ui
     if (lane == 0) {
       RateBin* bin = &bins[cu_key()];
       atomicAdd(&bin->ticks, static_cast<unsigned long long>(t1 - t0));
-      atomicAdd(&bin->waves, 1u);
+      atomicAdd(&bin->n, 1u);
     }
   }
 }
@@ -328,14 +323,6 @@ bool extras_ok(const ValuArgs& a, const ValuExtras& x) {
     return p.wave >= BGC_PLANT_ALL_WAVES && p.cls >= 0 && p.cls < ref::kRateClasses && p.ticks > 0 && p.ticks <= BGC_DIAG_MAX_DELAY_TICKS;
   });
   return check_ok && rate_ok && delays_ok && (!x.want_data || (x.data && x.wave >= 0));
-}
-
-template <class P>
-int upload(DeviceBuffer& d, const P* plants, int n) {
-  if (n == 0) return 0;
-  HIP_TRY(d.alloc(static_cast<size_t>(n) * sizeof(P)));
-  HIP_TRY(hipMemcpy(d.p, plants, static_cast<size_t>(n) * sizeof(P), hipMemcpyHostToDevice));
-  return 0;
 }
 
 // The 64-word vector that more than half of `waves` vectors (`stride` words apart) equal: its wave, or -1.
@@ -455,7 +442,7 @@ int rate_class(const RateRun& r, uint32_t a_bits, uint32_t b_bits, double ops_pe
   for (int w = 0; ok && w < r.waves; ++w) ok = std::memcmp(ends.data() + static_cast<size_t>(w) * 64, expect, sizeof(expect)) == 0;
   if (!ok) r.out->rate_ok = 0;
   const double ops = static_cast<double>(r.waves) * 64 * ref::kChains * iters * ops_per_step;
-  r.out->rate[kClass] = ms > 0 ? ops / (ms * 1e-3) / 1e12 : 0.0;
+  r.out->rate[kClass] = tera_per_s(ops, ms);
   r.out->rate_ms[kClass] = ms;
   r.out->elapsed_ms += ms;
   return 0;
@@ -472,13 +459,9 @@ int valu_run(int device, const ValuArgs& a, const ValuExtras& x, bgc_valu_result
   HIP_TRY(hipSetDevice(device));
   const int cus = cu_count(device), grid = cus * a.waves_per_simd, waves = grid * (kBlock / 64);
   out->cus = cus;
-  const bool beyond = std::any_of(x.check, x.check + x.n_check, [&](const bgc_valu_plant& p) { return p.wave >= waves; }) ||
-                      std::any_of(x.rate, x.rate + x.n_rate, [&](const bgc_valu_rate_plant& p) { return p.wave >= waves; }) ||
-                      std::any_of(x.delays, x.delays + x.n_delay, [&](const bgc_valu_delay_plant& p) { return p.wave >= waves; }) ||
-                      (x.want_data && x.wave >= waves);
-  if (beyond) {
-    g_last_error = "invalid arguments: plant in a wave beyond the launch";
-    return 1;
+  if (any_beyond(x.check, x.n_check, &bgc_valu_plant::wave, waves) || any_beyond(x.rate, x.n_rate, &bgc_valu_rate_plant::wave, waves) ||
+      any_beyond(x.delays, x.n_delay, &bgc_valu_delay_plant::wave, waves) || (x.want_data && x.wave >= waves)) {
+    return refuse(kWaveBeyond);
   }
   const size_t n_digests = static_cast<size_t>(waves) * ref::kClasses * 64, n_trans = static_cast<size_t>(kBlock / 64) * a.rounds * 5 * 64;
   const size_t n_raw = static_cast<size_t>(a.rounds) * ref::kRoundWords * 64;
@@ -492,7 +475,10 @@ int valu_run(int device, const ValuArgs& a, const ValuExtras& x, bgc_valu_result
     HIP_TRY(raw.alloc(n_raw * sizeof(uint32_t), true));
     HIP_TRY(rate_cu_keys.alloc(ref::kRateClasses * sizeof(int), true));
   }
-  if (upload(d_check, x.check, x.n_check) != 0 || upload(d_rate, x.rate, x.n_rate) != 0 || upload(d_delays, x.delays, x.n_delay) != 0) return 1;
+  if (upload_plants(d_check, x.check, x.n_check) != 0 || upload_plants(d_rate, x.rate, x.n_rate) != 0 ||
+      upload_plants(d_delays, x.delays, x.n_delay) != 0) {
+    return 1;
+  }
   Events ev;
   HIP_TRY(ev.create());
   float ms_check = 0.f;
@@ -535,18 +521,10 @@ int valu_run(int device, const ValuArgs& a, const ValuExtras& x, bgc_valu_result
   if (x.want_data) HIP_TRY(hipMemcpy(x.data->rate_cu_key, rate_cu_keys.p, sizeof(x.data->rate_cu_key), hipMemcpyDeviceToHost));
   std::vector<RateBin> h_bins(BGC_DIAG_MAX_CU_KEYS);
   HIP_TRY(hipMemcpy(h_bins.data(), bins.p, h_bins.size() * sizeof(RateBin), hipMemcpyDeviceToHost));
-  double fastest = 0, slowest = 0;  // mean ticks of a rate wave on a CU, the five timed launches together
-  for (int k = 0; k < BGC_DIAG_MAX_CU_KEYS; ++k) {
-    const RateBin& bin = h_bins[static_cast<size_t>(k)];
-    if (!bin.waves) continue;
-    const double ticks = static_cast<double>(bin.ticks) / bin.waves;
-    fastest = fastest == 0 ? ticks : std::min(fastest, ticks);
-    if (ticks > slowest) {
-      slowest = ticks;
-      out->slowest_cu_key = k;
-    }
-  }
-  out->cu_balance = slowest > 0 ? fastest / slowest : 0.0;
+  TimingFold fold;  // of the mean ticks of a rate wave on a CU, the five timed launches together
+  for (int k = 0; k < BGC_DIAG_MAX_CU_KEYS; ++k) fold.add(k, h_bins[static_cast<size_t>(k)].ticks, h_bins[static_cast<size_t>(k)].n, 1.0);
+  out->slowest_cu_key = fold.slowest_key;
+  out->cu_balance = fold.balance();
   return 0;
 }
 
