@@ -1,4 +1,4 @@
-"""HIP/CDNA4 GPU health kernels (native/gpu/hip/: hbm.hip, mfma.hip, lds.hip, cache.hip, valu.hip, gemm_soak.hip) exposed to Python.
+"""HIP/CDNA4 GPU health kernels (native/gpu/hip/: hbm.hip, mfma.hip, lds.hip, cache.hip, valu.hip, atomic.hip, gemm_soak.hip) exposed to Python.
 
 These are the only compute kernels in the framework: the reference controller has none
 (SURVEY §2.5).  They back the node agent's diagnostics before a GPU is advertised
@@ -18,6 +18,8 @@ These are the only compute kernels in the framework: the reference controller ha
   aggregate L2 read rate; then a pattern check and the read rate of the 256 MiB Infinity Cache
 * ``valu(device)``      — the vector ALU's integer, fp32, fp16, fp64, conversion, integer-dot and transcendental
   instructions on every SIMD, refereed by the host CPU and attributed to CU, SIMD and lane; then the vector rates
+* ``atomic(device)``    — every global and LDS atomic form (integer, 64-bit, fp32, fp64, packed bf16 / fp16 adds, compare-and-swap,
+  returning adds as tickets) in a table per workgroup and in one shared by the launch, refereed by the host CPU; then the atomic rates
 * ``gemm_check(device)``— a bf16 GEMM on the matrix cores checked element by element against
   a double-precision product of the same operands on the host
 * ``gemm_soak(device)`` — the sustained-throughput soak: the 8-phase ping-pong GEMM
@@ -32,11 +34,11 @@ These are the only compute kernels in the framework: the reference controller ha
 * ``pcie(device)``      — host<->device copy bandwidth, pinned
 * ``device_bdf(device)``— the HIP device's PCI address, to match it to amdsmi / kubelet
 * ``hbm_planted``, ``hbm_walk_planted``, ``pcie_planted``, ``mfma_planted``,
-  ``mfma_lowp_planted``, ``mfma_classic_planted``, ``lds_planted``, ``cache_planted``, ``valu_planted``, ``gemm_soak_planted``, ``burn_planted`` — for tests: the same diagnostics with wrong
+  ``mfma_lowp_planted``, ``mfma_classic_planted``, ``lds_planted``, ``cache_planted``, ``valu_planted``, ``atomic_planted``, ``gemm_soak_planted``, ``burn_planted`` — for tests: the same diagnostics with wrong
   values planted in their own data, to show that they are detected (see below)
-* ``mfma_delayed``, ``burn_delayed``, ``cache_delayed``, ``valu_delayed`` — for tests: the matrix-core throughput, the burn, the L2 rate and the vector rates with
+* ``mfma_delayed``, ``burn_delayed``, ``cache_delayed``, ``valu_delayed``, ``atomic_delayed`` — for tests: the matrix-core throughput, the burn, the L2 rate, the vector and the atomic rates with
   chosen waves, launches or workgroups made slow by a known time, to show that it reaches the rates
-* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile``, ``mfma_classic_tile``, ``lds_data``, ``cache_data``, ``valu_data``, ``valu_expected`` — for tests:
+* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile``, ``mfma_classic_tile``, ``lds_data``, ``cache_data``, ``valu_data``, ``valu_expected``, ``atomic_data``, ``atomic_expected``, ``atomic_rate_expected`` — for tests:
   the same diagnostics, returning the data they generated for themselves (see below)
 
 All fail loudly (RuntimeError) if ``libbgc_gpu_diag.so`` or the GPU is missing; there
@@ -165,6 +167,34 @@ def valu_trans_ulps():
     return tuple(native().diag_valu_trans_ulps())
 
 
+ATOMIC_PLACEMENTS = ("own", "shared")  # BGC_ATOMIC_OWN, _SHARED
+ATOMIC_CLASSES = ("int32", "int64", "f32", "f64", "pk16", "cas", "ticket", "lds")  # BGC_ATOMIC_*: the order of own_mismatches
+ATOMIC_CLASS_WORDS = (6, 2, 1, 2, 2, 1, 1, 9)  # 32-bit words of a class's element
+ATOMIC_CLASS_OPS = (6, 1, 1, 1, 2, 1, 1, 9)  # the words a plant can name
+ATOMIC_INT_WORDS = ("add", "smin", "umax", "and", "or", "xor")
+ATOMIC_LDS_WORDS = ("add", "ticket", "umax", "smin", "and", "or", "xor", "add_f32", "cas")
+ATOMIC_RATE_CLASSES = ("f32", "pk_bf16", "u32", "rtn")  # BGC_ATOMIC_RATE_*: the order of rate_ms
+ATOMIC_EMPTY = 0xFFFFFFFF
+# Defaults of atomic(), from tools/probes/atomic_rate_probe.py on the MI355X (profiles/atomic_diag/rates.json, 12 runs per point, each
+# right after an MFMA check).  rate_iters is odd, so that the float rows do not all end at 0: 4095 visits row 63 an odd number of times.
+# The rates rise with the iterations until the launch outlasts its ramp: the fp32 add reads 1.24-1.27 TB/s at 1023 iterations, 1.33-1.34
+# at 4095 and 1.35-1.36 at 16383, where the returning adds alone take 39 ms.  The run is 14.5 ms of kernels, 0.25 ms of them the check, and
+# 133-135 ms with its copies and the host referee, whose time follows the check's size: about 60 ms per workgroup per CU.
+ATOMIC_WGS_PER_CU = 2
+ATOMIC_ROUNDS = 8
+ATOMIC_RATE_ITERS = 4095
+
+
+def atomic(device=0, wgs_per_cu=ATOMIC_WGS_PER_CU, rounds=ATOMIC_ROUNDS, rate_iters=ATOMIC_RATE_ITERS, seed=0x5EED):
+    """Atomic read-modify-writes: cus * `wgs_per_cu` (1..8) workgroups of four waves each run `rounds` (1..64) rounds of every
+    class (ATOMIC_CLASSES) on hashed operands, in a table of the workgroup's own (``own_mismatches``; a wrong element names the
+    CU) and in one shared by the launch (``shared_mismatches``).  Every final value is independent of the order of arrival; the
+    host CPU recomputes the tables and checks every compare-and-swap and every ticket by its property.  Then each rate class
+    (ATOMIC_RATE_CLASSES) runs `rate_iters` (1..65536) iterations: ``f32_add_tbps``, ``pk_bf16_add_tbps``, ``u32_add_tbps``
+    (TB/s of added bytes), ``rtn_gops`` (10^9 returning adds per second); ``rate_ms`` in that order."""
+    return json.loads(native().diag_atomic(device, wgs_per_cu, rounds, rate_iters, seed))
+
+
 def gemm_check(device=0, m=4096, n=4096, k=4096, seed=0x5EED):
     return json.loads(native().diag_gemm_check(device, m, n, k, seed))
 
@@ -263,6 +293,29 @@ def valu_planted(check_plants, rate_plants=(), device=0, waves_per_simd=1, round
     check = [(p[0], _valu_code(VALU_CLASSES, p[1])) + tuple(p[2:]) for p in check_plants]
     rate = [(p[0], _valu_code(VALU_RATE_CLASSES, p[1])) + tuple(p[2:]) for p in rate_plants]
     return json.loads(native().diag_valu_planted(device, waves_per_simd, rounds, rate_iters, seed, check, rate))
+
+
+def _atomic_plants(plants):
+    """(placement, class, word, wave, round, lane, times, mask) with the placement and the class by name or number"""
+    return [(_valu_code(ATOMIC_PLACEMENTS, p[0]), _valu_code(ATOMIC_CLASSES, p[1])) + tuple(p[2:]) for p in plants]
+
+
+def _atomic_rate_plants(plants):
+    return [(_valu_code(ATOMIC_RATE_CLASSES, p[0]),) + tuple(p[1:]) for p in plants]
+
+
+def atomic_planted(plants, rate_plants=(), device=0, wgs_per_cu=1, rounds=2, rate_iters=15, seed=0x5EED):
+    """`plants` = [(placement, class, word of the element, wave, round, lane, times, xor mask), ...]: that lane issues that
+    atomic `times` (0..2) times, its operand word XORed with the mask.  `rate_plants` = [(rate class, wave, lane, times), ...]:
+    that lane issues the atomic of the last iteration of that class's timed launch `times` (0 or 2) times."""
+    return json.loads(native().diag_atomic_planted(device, wgs_per_cu, rounds, rate_iters, seed, _atomic_plants(plants),
+                                                   _atomic_rate_plants(rate_plants)))
+
+
+def atomic_delayed(delays, device=0, wgs_per_cu=1, rounds=2, rate_iters=15, seed=0x5EED):
+    """`delays` = [(rate class, wave or ALL_WAVES, ticks), ...]: in that class's timed rate launch that wave waits `ticks` of the
+    100 MHz constant clock after its loop and before it reads its end time.  No value is touched."""
+    return json.loads(native().diag_atomic_delayed(device, wgs_per_cu, rounds, rate_iters, seed, _atomic_rate_plants(delays)))
 
 
 MAX_DELAY_TICKS = 10_000_000  # 100 ms of the 100 MHz constant clock
@@ -402,6 +455,66 @@ def valu_expected(rounds, seed=0x5EED):
     """What the host referee expects of every wave, shaped as valu_data's wave (``cu_key``, ``simd`` and ``rate_cu_key`` -1; the
     trans words are double-precision libm rounded to fp32, which no digest is compared with).  Needs no GPU."""
     return _valu_wave(native().diag_valu_expected(seed, rounds), rounds)
+
+
+ATOMIC_LAYOUT = np.dtype([("grid", "<i4"), ("rate_grid", "<i4"), ("rounds", "<i4"), ("waves", "<i4"), ("pairs", "<u4"), ("rows", "<u4", (2, 8)),
+                          ("order_cap", "<u4", 3), ("table_off", "<u8", (2, 8)), ("data_off", "<u8", 8), ("data_words", "<u8", 8),
+                          ("total_words", "<u8")])  # bgc_atomic_layout
+
+
+def atomic_layout(grid, rounds, rate_grid=8):
+    """Where everything of a check launch of `grid` workgroups lies (bgc_atomic_layout), as a numpy record.  Needs no GPU."""
+    return np.frombuffer(native().diag_atomic_layout(grid, rate_grid, rounds), dtype=ATOMIC_LAYOUT)[0]
+
+
+def _atomic_block(layout, data):
+    """The sections of a data block: ``own`` and ``shared`` {class: [word, row, lane]; int64 and f64 [row, lane] uint64}, ``ballots``
+    [own / shared / lds, pair] uint64, ``order`` {own, shared, lds: [row, lane, slot]}, ``cu_keys`` [workgroup], ``rate_cu_keys``
+    [rate class, workgroup], and ``words``, the whole block."""
+    words = np.frombuffer(data, dtype="<u4")
+    assert words.size == int(layout["total_words"])
+
+    def section(s):
+        return words[int(layout["data_off"][s]):int(layout["data_off"][s]) + int(layout["data_words"][s])]
+
+    out = {"words": words, "layout": layout}
+    for pl, name in enumerate(ATOMIC_PLACEMENTS):
+        table, classes = section(pl), {}
+        for c, cls in enumerate(ATOMIC_CLASSES):
+            rows, first = int(layout["rows"][pl][c]), int(layout["table_off"][pl][c])
+            part = table[first:first + rows * 64 * ATOMIC_CLASS_WORDS[c]]
+            classes[cls] = part.view("<u8").reshape(rows, 64) if cls in ("int64", "f64") else part.reshape(ATOMIC_CLASS_WORDS[c], rows, 64)
+        out[name] = classes
+    out["ballots"] = section(2).view("<u8").reshape(3, int(layout["pairs"]))
+    out["order"] = {name: section(3 + k).reshape(-1, 64, int(layout["order_cap"][k])) for k, name in enumerate(("own", "shared", "lds"))}
+    out["cu_keys"] = section(6).view("<i4")
+    out["rate_cu_keys"] = section(7).view("<i4").reshape(4, int(layout["rate_grid"]))
+    return out
+
+
+def atomic_data(plants=(), rate_plants=(), delays=(), device=0, wgs_per_cu=1, rounds=2, rate_iters=15, seed=0x5EED):
+    """(result, data of that run) with the plants of atomic_planted and the delays of atomic_delayed applied: the final tables, the
+    winners' ballots, the order arrays and the CU key that every workgroup recorded, in the check launch and in each timed rate
+    launch (see _atomic_block)."""
+    r, data = native().diag_atomic_data(device, wgs_per_cu, rounds, rate_iters, seed, _atomic_plants(plants), _atomic_rate_plants(rate_plants),
+                                        _atomic_rate_plants(delays))
+    r = json.loads(r)
+    return r, _atomic_block(atomic_layout(r["cus"] * wgs_per_cu, rounds, (2 * r["cus"] + 7) // 8 * 8), data)
+
+
+def atomic_expected(grid, rounds, plants=(), seed=0x5EED):
+    """The host referee's tables for a launch of `grid` workgroups with `plants` applied, shaped as atomic_data's (the CU keys
+    -1).  Every cas goes to the contender with the lowest pair and every ticket is drawn in the order of the pairs: one admissible
+    outcome of what the hardware's order decides.  Needs no GPU."""
+    return _atomic_block(atomic_layout(grid, rounds), native().diag_atomic_expected(seed, grid, rounds, _atomic_plants(plants)))
+
+
+def atomic_rate_expected(rate_grid, rate_iters, cls, seed=0x5EED):
+    """The end values of rate class `cls` for `rate_grid` workgroups: [group, row, lane] uint32 (f32: float bits; pk_bf16: packed),
+    or the groups' heads of "rtn".  Needs no GPU."""
+    code = _valu_code(ATOMIC_RATE_CLASSES, cls)
+    out = np.frombuffer(native().diag_atomic_rate_expected(seed, rate_grid, rate_iters, code), dtype="<u4")
+    return out if code == 3 else out.reshape(-1, 64, 64)
 
 
 def _bf16_bytes(x):

@@ -301,6 +301,54 @@ json::Value to_json(int device, const bgc_valu_result& r) {
                               {"passed", clean && r.consensus_ok != 0 && r.trans_out_of_bound == 0 && r.rate_ok != 0}});
 }
 
+json::Value to_json(int device, const bgc_atomic_result& r) {
+  static const char* const kClasses[BGC_ATOMIC_CLASSES] = {"int32", "int64", "f32", "f64", "pk16", "cas", "ticket", "lds"};
+  json::Value own = json::Value::array(), shared = json::Value::array(), rate_ms = json::Value::array();
+  json::Value xw = json::Value::array(), xus = json::Value::array();
+  uint64_t mism = 0;
+  for (int c = 0; c < BGC_ATOMIC_CLASSES; ++c) {
+    own.push_back(static_cast<unsigned long long>(r.mismatches[BGC_ATOMIC_OWN][c]));
+    shared.push_back(static_cast<unsigned long long>(r.mismatches[BGC_ATOMIC_SHARED][c]));
+    mism += r.mismatches[BGC_ATOMIC_OWN][c] + r.mismatches[BGC_ATOMIC_SHARED][c];
+  }
+  for (int c = 0; c < BGC_ATOMIC_RATE_CLASSES; ++c) rate_ms.push_back(r.rate_ms[c]);
+  for (int x = 0; x < 8; ++x) {
+    xw.push_back(r.xcc_waves[x]);
+    xus.push_back(r.xcc_us[x]);
+  }
+  char bits[24];
+  std::snprintf(bits, sizeof(bits), "0x%016llx", static_cast<unsigned long long>(r.first_bad_xor));
+  const bool clean = mism == 0;
+  return json::Value::object({{"device", device},
+                              {"cus", r.cus},
+                              {"cus_seen", r.cus_seen},
+                              {"values_checked", static_cast<unsigned long long>(r.values_checked)},
+                              {"own_mismatches", own},  // int32, int64, f32, f64, pk16, cas, ticket, lds
+                              {"shared_mismatches", shared},
+                              {"mismatches", static_cast<unsigned long long>(mism)},
+                              {"bad_cus", r.bad_cus},
+                              {"bad_cu_keys", bad_cu_keys(r)},
+                              {"first_bad_placement", clean ? json::Value() : json::Value(std::string(r.first_bad_placement == BGC_ATOMIC_OWN ? "own" : "shared"))},
+                              {"first_bad_class", clean ? json::Value() : json::Value(std::string(kClasses[r.first_bad_class]))},
+                              {"first_bad_op", clean ? json::Value() : json::Value(r.first_bad_op)},
+                              {"first_bad_element", clean ? json::Value() : json::Value(static_cast<long long>(r.first_bad_element))},
+                              {"first_bad_xor", clean ? json::Value() : json::Value(std::string(bits))},
+                              {"first_bad_delta", clean ? json::Value() : json::Value(static_cast<long long>(r.first_bad_delta))},
+                              {"tickets_out_of_range", static_cast<unsigned long long>(r.tickets_out_of_range)},
+                              {"f32_add_tbps", r.rate[BGC_ATOMIC_RATE_F32]},
+                              {"pk_bf16_add_tbps", r.rate[BGC_ATOMIC_RATE_PK_BF16]},
+                              {"u32_add_tbps", r.rate[BGC_ATOMIC_RATE_U32]},
+                              {"rtn_gops", r.rate[BGC_ATOMIC_RATE_RTN]},
+                              {"rate_ms", rate_ms},  // f32, pk bf16, u32, rtn
+                              {"rate_ok", r.rate_ok != 0},
+                              {"xcc_waves", xw},
+                              {"xcc_us", xus},
+                              {"slowest_xcc", r.slowest_xcc},
+                              {"xcc_balance", r.xcc_balance},
+                              {"elapsed_ms", r.elapsed_ms},
+                              {"passed", clean && r.tickets_out_of_range == 0 && r.rate_ok != 0}});
+}
+
 json::Value to_json(int device, const bgc_pcie_result& r) {
   return json::Value::object({{"device", device}, {"bytes", static_cast<unsigned long long>(r.bytes)},
                               {"iters", r.iters}, {"h2d_gbps", r.h2d_gbps}, {"d2h_gbps", r.d2h_gbps},
@@ -368,6 +416,10 @@ json::Value Diag::cache(int device, int rounds, uint32_t region_bytes, int l2_sw
 
 json::Value Diag::valu(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed) {
   return call("valu diag", valu_, device, waves_per_simd, rounds, rate_iters, seed);
+}
+
+json::Value Diag::atomic(int device, int wgs_per_cu, int rounds, int rate_iters, uint32_t seed) {
+  return call("atomic diag", atomic_, device, wgs_per_cu, rounds, rate_iters, seed);
 }
 
 json::Value Diag::pcie(int device, uint64_t bytes, int iters, uint32_t seed) {

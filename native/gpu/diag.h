@@ -101,6 +101,7 @@ json::Value to_json(int device, const bgc_classic_result& r);
 json::Value to_json(int device, const bgc_lds_result& r);
 json::Value to_json(int device, const bgc_cache_result& r);
 json::Value to_json(int device, const bgc_valu_result& r);
+json::Value to_json(int device, const bgc_atomic_result& r);
 json::Value to_json(int device, const bgc_pcie_result& r);
 json::Value to_json(int device, const bgc_soak_result& r);
 json::Value to_json(int device, const bgc_hbm_walk_result& r);
@@ -126,6 +127,8 @@ class Diag {
   json::Value cache(int device, int rounds, uint32_t region_bytes, int l2_sweeps, uint64_t ic_bytes, int ic_sweeps, uint32_t seed);
   // Per-SIMD check of the vector ALU's instruction classes, refereed by the host, and the vector rates (see bgc_diag_valu).
   json::Value valu(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed);
+  // Check of every global and LDS atomic form, refereed by the host, and the atomic rates (see bgc_diag_atomic).
+  json::Value atomic(int device, int wgs_per_cu, int rounds, int rate_iters, uint32_t seed);
   // MFMA GEMM on the device vs a host fp32 product of the same bf16 operands
   // (deterministic pseudo-random values in [-1, 1]).  Returns max error and the bound.
   json::Value gemm_check(int device, int m, int n, int k, uint32_t seed);
@@ -188,6 +191,7 @@ class Diag {
   BGC_DIAG_ENTRY(lds_, bgc_diag_lds);
   BGC_DIAG_ENTRY(cache_, bgc_diag_cache);
   BGC_DIAG_ENTRY(valu_, bgc_diag_valu);
+  BGC_DIAG_ENTRY(atomic_, bgc_diag_atomic);
   BGC_DIAG_ENTRY(burn_, bgc_diag_burn_dtype);
   BGC_DIAG_ENTRY(soak_, bgc_diag_gemm_soak);
   BGC_DIAG_ENTRY(gemm_, bgc_diag_gemm);

@@ -140,6 +140,47 @@ extern "C" {
 //    x = 0.25 + (l + 64 chain) / 1024, which settles at 1.  The end digest of a lane starts at 0x85ebca6b + rate
 //    class and folds chain 0's words, then chain 1's, ... (fp32: component 0, component 1; fp16: one packed word;
 //    fp64: low, high); the host computes it for the four exact classes and takes the waves' consensus for trans.
+//  * Atomics (bgc_diag_atomic).  A launch is `grid` workgroups of four waves; wave w = 4 * workgroup + wave of the
+//    workgroup, pair p = w * rounds + r for round r, P = 4 * grid * rounds pairs in all.  Operand word k of
+//    (class cls, wave w, round r, lane l) is
+//      a(cls, k, w, r, l) = mix32(mix32(seed ^ mix32(cls << 4 | k)) ^ (w << 12 | r << 6 | l)).
+//    Every operation is chosen so that the final value of an element does not depend on the order in which its
+//    operations arrive.  A class's table is rows of 64 elements.  In placement OWN it has 2 * grid rows and (w, r)
+//    works on row 2 * workgroup + (w + r) mod 2, so the 2 * rounds pairs of one workgroup share a row; in placement
+//    SHARED it has rows_cls = ceil(P / N_cls) rows and (w, r) works on row p mod rows_cls, so no element has more
+//    than N_cls operations (N: int32, int64, f32 and f64 4096, pk16 128, cas and ticket 64).  Lane l works on
+//    element l of the row.  Word k of a 32-bit class's element is at (k * rows + row) * 64 + l words into the class's
+//    table, a 64-bit class's element at (row * 64 + l) * 2.
+//      int32 (6 words), a_k = a(0, k, ..):  word 0 += a_0 modulo 2^32 from 0;  word 1 = min of the a_1 as signed
+//        from 0x7fffffff;  word 2 = max of the a_2 as unsigned from 0;  word 3 &= a_3 from 0xffffffff;  word 4 |= a_4
+//        from 0;  word 5 ^= a_5 from 0.
+//      int64:  += a(1, 1, ..) << 32 | a(1, 0, ..) modulo 2^64 from 0.
+//      f32:  += (a mod 4095) - 2047 as a float from 0.  |sum| <= 2047 * 4096 < 2^24 at any point of any order, so
+//        every partial sum is exact.
+//      f64:  += int(a >> 6) - 2^25 as a double from 0; |sum| <= 2^25 * 4096 = 2^37 < 2^53.
+//      pk16 (2 words):  word 0 += (trit(a(4, 0, ..)), trit(a(4, 0, ..) >> 16)) as packed bf16, the first in the low
+//        half;  word 1 the same of a(4, 1, ..) as packed fp16.  At most 128 operations, so every partial sum is an
+//        integer of magnitude <= 128, exact in bf16 (8 significand bits) and in fp16.
+//      cas:  every lane tries once to replace BGC_ATOMIC_EMPTY by its id = p * 64 + l and the wave stores the
+//        ballot of the lanes that succeeded.  Exactly one of an element's contenders wins, and the element holds
+//        the winner's id; which one wins is the hardware's choice.
+//      ticket:  every lane adds 1 to the element, a counter from 0, takes the value before as its ticket and writes
+//        id + 1 to slot `ticket` of the element's order array (capacity: OWN and LDS 2 * rounds, SHARED
+//        ceil(P / rows)), if the ticket is below the capacity.  The counter ends at its number of pullers and the
+//        order array is a permutation of their id + 1.
+//      lds (9 words, OWN only, the table in the workgroup's LDS and copied out at the end), a_k = a(7, k, ..):
+//        word 0 += a_0;  word 1 a ticket counter as above;  word 2 max unsigned of a_2;  word 3 min signed of a_3;
+//        word 4 &= a_4;  word 5 |= a_5;  word 6 ^= a_6;  word 7 += (a_7 mod 4095) - 2047 as a float;  word 8 a cas
+//        as above.  Initial values as in int32.
+//    Rate phase: `rate_grid` workgroups (a multiple of 8), group g = (workgroup / 8) * 4 + wave of the workgroup, so
+//    a group has the 8 waves of equal number of 8 consecutive workgroups.  A group owns 64 rows of 64 32-bit words;
+//    in iteration i its waves add to row i mod 64, lane l to word l, for the visit j = i / 64.  With
+//    h(cls, w, l) = mix32(mix32(seed ^ mix32(0x100 | cls)) ^ (w << 6 | l)):  f32 adds (-1)^j trit(h) as a float;  pk
+//    bf16 adds (-1)^j (trit(h), trit(h >> 16)) as packed bf16;  u32 adds h + i * 0x9e3779b9 modulo 2^32;  rtn: lane
+//    0 adds 1 to the group's head and sums the values it gets back.  The sign follows the visit, so whatever an
+//    adder has added to one word is 0 or its trit at any time, a word's partial sums stay within +-8 in any order,
+//    and a word ends at the sum of the trits of its adders if it was visited an odd number of times, else at 0.
+//    A head ends at n = 8 * iters and the group's sums total n (n - 1) / 2.
 
 typedef struct {
   uint64_t bytes;          // buffer size tested
@@ -442,6 +483,59 @@ typedef struct {
 // (1..65536) iterations of 8 chains per lane.  Not covered: the scalar ALU, the floating-point dot products
 // (their internal rounding is unspecified), fp8 conversions and the register file as a memory.
 int bgc_diag_valu(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed, bgc_valu_result* out);
+// The atomic check's placements and classes, in the order of mismatches[2][8] below and of a plant's fields.
+#define BGC_ATOMIC_OWN 0     // a table of the workgroup's own: its 4 waves contend, a wrong element names the CU
+#define BGC_ATOMIC_SHARED 1  // one table for the launch: waves of workgroups far apart contend
+#define BGC_ATOMIC_INT32 0   // global_atomic_add, _smin, _umax, _and, _or, _xor
+#define BGC_ATOMIC_INT64 1   // global_atomic_add_x2
+#define BGC_ATOMIC_F32 2     // global_atomic_add_f32
+#define BGC_ATOMIC_F64 3     // global_atomic_add_f64
+#define BGC_ATOMIC_PK16 4    // global_atomic_pk_add_bf16, global_atomic_pk_add_f16
+#define BGC_ATOMIC_CAS 5     // global_atomic_cmpswap, returning, one try per lane
+#define BGC_ATOMIC_TICKET 6  // global_atomic_add, returning
+#define BGC_ATOMIC_LDS 7     // ds_add_u32, ds_add_rtn_u32, ds_max_u32, ds_min_i32, ds_and_b32, ds_or_b32, ds_xor_b32, ds_add_f32, ds_cmpst_rtn_b32; OWN only
+#define BGC_ATOMIC_CLASSES 8
+#define BGC_ATOMIC_EMPTY 0xffffffffu  // a cas element nobody has claimed
+// The rate phase's classes, in the order of every [4] below.
+#define BGC_ATOMIC_RATE_F32 0      // global_atomic_add_f32 without return, TB/s of added bytes
+#define BGC_ATOMIC_RATE_PK_BF16 1  // global_atomic_pk_add_bf16 without return, TB/s of added bytes
+#define BGC_ATOMIC_RATE_U32 2      // global_atomic_add without return, TB/s of added bytes
+#define BGC_ATOMIC_RATE_RTN 3      // global_atomic_add with return by lane 0 of each wave, 1e9 adds/s
+#define BGC_ATOMIC_RATE_CLASSES 4
+typedef struct {
+  int cus;                       // CUs of the device
+  int cus_seen;                  // distinct CUs that ran a check workgroup
+  uint64_t values_checked;       // 32-bit words of both tables and slots of the order arrays that the host judged
+  uint64_t mismatches[2][8];     // [placement][class]: wrong words (64-bit classes: values; cas, ticket: elements)
+  int bad_cus;                   // CUs whose workgroup has a wrong OWN or LDS element
+  int first_bad_placement;       // the first wrong value in the order OWN, SHARED and class, word, row, lane; each -1 if none
+  int first_bad_class;
+  int first_bad_op;              // word of the element
+  int64_t first_bad_element;     // row * 64 + lane in the class's table
+  uint64_t first_bad_xor;        // expected ^ found (cas, ticket: 0)
+  int64_t first_bad_delta;       // found - expected of an add word: modulo 2^32 or 2^64 as signed, a float's as an integer
+                                 // (pk16: of the low half, of the high half if the low one is right); else 0
+  uint64_t tickets_out_of_range; // tickets at or beyond their order array's capacity: counted, nothing stored
+  double rate[4];                // each rate class's timed launch: TB/s of added bytes, rtn 1e9 adds/s
+  double rate_ms[4];             // device time of that launch
+  int rate_ok;                   // every end value of every rate launch matched its closed form
+  int xcc_waves[8];              // rate waves that ran on each XCC, the four timed launches together
+  double xcc_us[8];              // mean time of their loops (constant 100 MHz clock)
+  int slowest_xcc;               // -1 if none ran
+  double xcc_balance;            // fastest / slowest XCC mean loop time (1.0 = balanced)
+  double elapsed_ms;             // the check launch and the four timed launches
+  int bad_cu_keys[64];
+} bgc_atomic_result;
+
+// Atomic read-modify-writes, which every scatter, index_add, split-K and attention-backward accumulation, histogram
+// and cross-workgroup ticket or claim relies on: cus * `wgs_per_cu` (1..8) workgroups of four waves each run `rounds`
+// (1..64) rounds of every class above on hashed operands, in a table of their own and in one shared by the launch
+// ("Atomics", above).  No wave waits for another, no operation is tried again, and a returned ticket is used as an
+// index only below the capacity of its array.  The device compares nothing: the final tables go to the host, which
+// recomputes them (atomic_ref.h).  Then a warm-up and a timed launch per rate class, `rate_iters` (1..65536)
+// iterations, each wave instruction 256 contiguous bytes, 8 adders per word, the end values checked against their
+// closed forms and the waves' loop times binned by XCC (reported only).  Agent scope and device memory only.
+int bgc_diag_atomic(int device, int wgs_per_cu, int rounds, int rate_iters, uint32_t seed, bgc_atomic_result* out);
 // ---------------------------------------------------------------------------------------------
 // Planted variants: FOR TESTS ONLY.  Each runs the same implementation as the entry point it is
 // named after, with a list of deliberately wrong values ("plants") written into the diagnostic's
@@ -643,6 +737,33 @@ typedef struct {
 int bgc_diag_valu_delayed(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed, const bgc_valu_delay_plant* delays,
                           int n, bgc_valu_result* out);
 
+// Lane `lane` of check wave `wave` (global wave index, below the launch's cus * wgs_per_cu * 4) issues the atomic
+// of word `op` (below the class's word count; 0 for int64, f32, f64, cas and ticket) of class `cls` in placement
+// `placement` in round `round` `times` times instead of once: 0 is a lost update, 2 a doubled one, 1 with a non-zero
+// mask a wrong operand.  The operand word (the hash a(cls, op, ..), of int64 its low word; the id of cas and ticket)
+// is XORed with the mask.  Of several plants on one atomic the first in the list applies.  times 0..2, and a zero
+// mask with times 1 is refused; LDS takes placement OWN only.
+typedef struct {
+  int placement, cls, op, wave, round, lane, times;
+  uint32_t xor_mask;
+} bgc_atomic_plant;
+// Lane `lane` (rtn: 0) of wave `wave` of rate class `cls`'s timed launch issues the atomic of its last iteration
+// `times` (0 or 2) times.
+typedef struct {
+  int cls, wave, lane, times;
+} bgc_atomic_rate_plant;
+int bgc_diag_atomic_planted(int device, int wgs_per_cu, int rounds, int rate_iters, uint32_t seed, const bgc_atomic_plant* plants, int n,
+                            const bgc_atomic_rate_plant* rate, int n_rate, bgc_atomic_result* out);
+// Wave `wave` (or every one, BGC_PLANT_ALL_WAVES) of rate class `cls`'s timed launch waits `ticks`
+// (1..BGC_DIAG_MAX_DELAY_TICKS) of the constant clock after its loop and before it reads its end time.  No value is
+// touched: the time shows in rate, rate_ms, xcc_us, slowest_xcc and xcc_balance only.
+typedef struct {
+  int cls, wave;
+  uint32_t ticks;
+} bgc_atomic_delay_plant;
+int bgc_diag_atomic_delayed(int device, int wgs_per_cu, int rounds, int rate_iters, uint32_t seed, const bgc_atomic_delay_plant* delays,
+                            int n, bgc_atomic_result* out);
+
 // ---------------------------------------------------------------------------------------------
 // Generated data: FOR TESTS ONLY, never loaded by the node agent or the diag worker.  Each runs
 // the same implementation as the entry point it is named after and then copies the data that
@@ -724,6 +845,45 @@ int bgc_diag_valu_data(int device, int waves_per_simd, int rounds, int rate_iter
 // The host referee's values for (seed, rounds): the digests it compares with, and every result word (trans: double
 // libm rounded to float, which no digest is compared with).  Touches no device.
 int bgc_diag_valu_expected(uint32_t seed, int rounds, bgc_valu_wave* data);
+
+// Where everything of an atomic check with `grid` workgroups, `rounds` rounds and a rate phase of `rate_grid`
+// workgroups lies ("Atomics", above), and the data the two entries below return: 32-bit words in this order, each
+// section at data_off[] words from the start.
+#define BGC_ATOMIC_DATA_OWN 0           // the OWN table: class cls at table_off[0][cls] words, rows[0][cls] rows
+#define BGC_ATOMIC_DATA_SHARED 1        // the SHARED table alike, with [1]
+#define BGC_ATOMIC_DATA_BALLOTS 2       // 64-bit winners' ballots of the cas: [OWN, SHARED, LDS][pair]
+#define BGC_ATOMIC_DATA_ORDER_OWN 3     // (row * 64 + lane) * order_cap[0] + ticket
+#define BGC_ATOMIC_DATA_ORDER_SHARED 4  // alike with order_cap[1]
+#define BGC_ATOMIC_DATA_ORDER_LDS 5     // alike with order_cap[2]
+#define BGC_ATOMIC_DATA_CU_KEYS 6       // the CU key each check workgroup recorded
+#define BGC_ATOMIC_DATA_RATE_CU_KEYS 7  // [rate class][workgroup of the timed rate launch]
+#define BGC_ATOMIC_DATA_SECTIONS 8
+typedef struct {
+  int grid, rate_grid, rounds, waves;
+  uint32_t pairs;              // waves * rounds
+  uint32_t rows[2][8];         // rows of a class's table (SHARED LDS: 0)
+  uint32_t order_cap[3];       // slots of an element's order array: OWN, SHARED, LDS
+  uint64_t table_off[2][8];    // first word of a class in its placement's table
+  uint64_t data_off[8];
+  uint64_t data_words[8];
+  uint64_t total_words;
+} bgc_atomic_layout;
+// grid 1..16384, rate_grid a multiple of 8 in 8..4096, rounds 1..64.  Touches no device.
+int bgc_diag_atomic_layout(int grid, int rate_grid, int rounds, bgc_atomic_layout* out);
+// bgc_diag_atomic with the plants of bgc_diag_atomic_planted and the delays of bgc_diag_atomic_delayed (any list may
+// be empty); then the final tables, the ballots, the order arrays and the CU keys of that very run to `data`, which
+// holds `capacity` bytes (at most BGC_DIAG_MAX_DATA_BYTES; a device whose data exceeds it is refused once its CU
+// count is known).
+int bgc_diag_atomic_data(int device, int wgs_per_cu, int rounds, int rate_iters, uint32_t seed, const bgc_atomic_plant* plants, int n,
+                         const bgc_atomic_rate_plant* rate, int n_rate, const bgc_atomic_delay_plant* delays, int n_delay, void* data,
+                         uint64_t capacity, bgc_atomic_result* out);
+// The host referee's tables for a launch of `grid` workgroups with `plants` applied, in the same layout (rate_grid
+// taken as 8, the CU keys -1).  Of what the hardware's order decides it gives one admissible outcome: every cas goes
+// to the contender with the lowest pair and every ticket is drawn in the order of the pairs.  Touches no device.
+int bgc_diag_atomic_expected(uint32_t seed, int grid, int rounds, const bgc_atomic_plant* plants, int n, void* data, uint64_t capacity);
+// The rate phase's end values for `rate_grid` workgroups: the groups' rows, (group * 64 + row) * 64 + lane, of classes
+// f32, pk bf16 and u32 (rate_grid / 8 * 4 * 4096 words), the groups' heads of rtn (rate_grid / 8 * 4 words).
+int bgc_diag_atomic_rate_expected(uint32_t seed, int rate_grid, int rate_iters, int cls, uint32_t* out, uint64_t capacity_words);
 
 // PCI bus id of a HIP device ("0000:05:00.0", lower-case hex) — the key the node agent and
 // the RCCL probe use to match a HIP device (renumbered inside a container) to amdsmi.

@@ -10,6 +10,8 @@
 //    pattern check and read rate;
 //  * valu.hip: the per-SIMD vector-ALU check (integer, fp32, fp16, fp64, conversions, integer dots and
 //    transcendentals, refereed by the host through valu_ref.h) and the vector rates;
+//  * atomic.hip: the check of every global and LDS atomic form in a table per workgroup and in one shared by the
+//    launch, refereed by the host through atomic_ref.h, and the atomic rates;
 //  * gemm_soak.hip: the ABFT-checked LDS-tiled GEMMs (gemm_soak and the 8-phase gemm_pingpong).
 // The design notes in those files follow the CDNA4 guides (cdna_hip_programming.md,
 // MI355X_MICROARCH.md).

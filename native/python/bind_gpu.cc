@@ -107,6 +107,13 @@ std::string planted(const char* what, Fn entry, A... args) {
   return dump_nogil([&] { return bgc::gpu::Diag::instance().call(what, entry, args...); });
 }
 
+using AtomicPlant = std::tuple<int, int, int, int, int, int, int, unsigned>;  // placement, class, word, wave, round, lane, times, mask
+std::vector<bgc_atomic_plant> atomic_plants(const std::vector<AtomicPlant>& plants) {
+  std::vector<bgc_atomic_plant> c;
+  for (const auto& [placement, cls, op, wave, round, lane, times, mask] : plants) c.push_back({placement, cls, op, wave, round, lane, times, mask});
+  return c;
+}
+
 using AccPlant = std::tuple<int, int, int, int, float>;       // check: wave, round, lane, i, delta; rate: wave, lane, chain, i, delta
 using LowpPlant = std::tuple<int, int, int, int, int, float>;  // the variant or path (check), the format or path (rate) or the burn's launch in front
 
@@ -260,6 +267,9 @@ void register_gpu(py::module_& m) {
   m.def("diag_valu", [](int device, int waves_per_simd, int rounds, int rate_iters, unsigned seed) {
     return dump_nogil([&] { return Diag::instance().valu(device, waves_per_simd, rounds, rate_iters, seed); });
   }, py::arg("device"), py::arg("waves_per_simd") = 2, py::arg("rounds") = 16, py::arg("rate_iters") = 16384, py::arg("seed") = 0x5eed);
+  m.def("diag_atomic", [](int device, int wgs_per_cu, int rounds, int rate_iters, unsigned seed) {
+    return dump_nogil([&] { return Diag::instance().atomic(device, wgs_per_cu, rounds, rate_iters, seed); });
+  }, py::arg("device"), py::arg("wgs_per_cu") = 2, py::arg("rounds") = 8, py::arg("rate_iters") = 4095, py::arg("seed") = 0x5eed);
   m.def("diag_gemm", [](int device, int mm, int nn, int kk, const std::string& a, const std::string& b) {
     if (a.size() != static_cast<size_t>(mm) * kk * 2 || b.size() != static_cast<size_t>(kk) * nn * 2) {
       throw std::invalid_argument("A must be M*K and B K*N bf16 values");
@@ -412,6 +422,22 @@ void register_gpu(py::module_& m) {
     for (const auto& [wave, cls, ticks] : delays) d.push_back({wave, cls, ticks});
     return planted("valu diag", BGC_DIAG_ENTRY(bgc_diag_valu_delayed), device, waves_per_simd, rounds, rate_iters, seed, d.data(), count(d));
   }, py::arg("device"), py::arg("waves_per_simd"), py::arg("rounds"), py::arg("rate_iters"), py::arg("seed"), py::arg("delays"));
+  // plants (placement, class, word, wave, round, lane, times, mask) and rate plants (rate class, wave, lane, times)
+  m.def("diag_atomic_planted", [](int device, int wgs_per_cu, int rounds, int rate_iters, unsigned seed, const std::vector<AtomicPlant>& plants,
+                                  const std::vector<std::tuple<int, int, int, int>>& rate_plants) {
+    const std::vector<bgc_atomic_plant> c = atomic_plants(plants);
+    std::vector<bgc_atomic_rate_plant> r;
+    for (const auto& [cls, wave, lane, times] : rate_plants) r.push_back({cls, wave, lane, times});
+    return planted("atomic diag", BGC_DIAG_ENTRY(bgc_diag_atomic_planted), device, wgs_per_cu, rounds, rate_iters, seed, c.data(), count(c),
+                   r.data(), count(r));
+  }, py::arg("device"), py::arg("wgs_per_cu"), py::arg("rounds"), py::arg("rate_iters"), py::arg("seed"), py::arg("plants"), py::arg("rate_plants"));
+  // (rate class, wave or -1, ticks of the constant clock) in that class's timed rate launch
+  m.def("diag_atomic_delayed", [](int device, int wgs_per_cu, int rounds, int rate_iters, unsigned seed,
+                                  const std::vector<std::tuple<int, int, unsigned>>& delays) {
+    std::vector<bgc_atomic_delay_plant> d;
+    for (const auto& [cls, wave, ticks] : delays) d.push_back({cls, wave, ticks});
+    return planted("atomic diag", BGC_DIAG_ENTRY(bgc_diag_atomic_delayed), device, wgs_per_cu, rounds, rate_iters, seed, d.data(), count(d));
+  }, py::arg("device"), py::arg("wgs_per_cu"), py::arg("rounds"), py::arg("rate_iters"), py::arg("seed"), py::arg("delays"));
   // Delay plants: (wave or -1, ticks of the constant clock) in the timed throughput launch; and a burn
   // whose launches from `first_delayed_launch` on have every wave delayed by `ticks`.
   m.def("diag_mfma_delayed", [](int device, int waves_per_cu, int iters, unsigned seed,
@@ -555,6 +581,57 @@ void register_gpu(py::module_& m) {
     Diag::instance().check("valu diag", BGC_DIAG_ENTRY(bgc_diag_valu_expected)(seed, rounds, reinterpret_cast<bgc_valu_wave*>(data.data())));
     return py::bytes(data);
   }, py::arg("seed"), py::arg("rounds"));
+  // bgc_atomic_layout as bytes; the result and the run's data block (sized for a device of up to 512 CUs, and at most the
+  // library's cap, where a larger run is refused) as bytes; the referee's block; a rate class's end values
+  m.def("diag_atomic_layout", [](int grid, int rate_grid, int rounds) {
+    std::string layout(sizeof(bgc_atomic_layout), '\0');
+    Diag::instance().check("atomic diag", BGC_DIAG_ENTRY(bgc_diag_atomic_layout)(grid, rate_grid, rounds, reinterpret_cast<bgc_atomic_layout*>(layout.data())));
+    return py::bytes(layout);
+  }, py::arg("grid"), py::arg("rate_grid"), py::arg("rounds"));
+  m.def("diag_atomic_data", [](int device, int wgs_per_cu, int rounds, int rate_iters, unsigned seed, const std::vector<AtomicPlant>& plants,
+                               const std::vector<std::tuple<int, int, int, int>>& rate_plants, const std::vector<std::tuple<int, int, unsigned>>& delays) {
+    const std::vector<bgc_atomic_plant> c = atomic_plants(plants);
+    std::vector<bgc_atomic_rate_plant> r;
+    std::vector<bgc_atomic_delay_plant> d;
+    for (const auto& [cls, wave, lane, times] : rate_plants) r.push_back({cls, wave, lane, times});
+    for (const auto& [cls, wave, ticks] : delays) d.push_back({cls, wave, ticks});
+    bgc_atomic_layout layout{};
+    u64 capacity = 0;
+    if (wgs_per_cu >= 1 && wgs_per_cu <= 8 && BGC_DIAG_ENTRY(bgc_diag_atomic_layout)(512 * wgs_per_cu, 1024, rounds, &layout) == 0) {
+      capacity = std::min<u64>(layout.total_words * 4, BGC_DIAG_MAX_DATA_BYTES);
+    }
+    std::string data(capacity, '\0');
+    Value v;
+    {
+      py::gil_scoped_release nogil;
+      v = Diag::instance().call("atomic diag", BGC_DIAG_ENTRY(bgc_diag_atomic_data), device, wgs_per_cu, rounds, rate_iters, seed, c.data(), count(c),
+                                r.data(), count(r), d.data(), count(d), static_cast<void*>(data.data()), capacity);
+    }
+    const int cus = static_cast<int>(v.get("cus").as_int());
+    Diag::instance().check("atomic diag", BGC_DIAG_ENTRY(bgc_diag_atomic_layout)(cus * wgs_per_cu, (2 * cus + 7) / 8 * 8, rounds, &layout));
+    data.resize(layout.total_words * 4);
+    return py::make_tuple(v.dump(), py::bytes(data));
+  }, py::arg("device"), py::arg("wgs_per_cu"), py::arg("rounds"), py::arg("rate_iters"), py::arg("seed"), py::arg("plants"), py::arg("rate_plants"),
+     py::arg("delays"));
+  m.def("diag_atomic_expected", [](unsigned seed, int grid, int rounds, const std::vector<AtomicPlant>& plants) {
+    const std::vector<bgc_atomic_plant> c = atomic_plants(plants);
+    bgc_atomic_layout layout{};
+    const bool sized = BGC_DIAG_ENTRY(bgc_diag_atomic_layout)(grid, 8, rounds, &layout) == 0 && layout.total_words * 4 <= BGC_DIAG_MAX_DATA_BYTES;
+    std::string data(sized ? layout.total_words * 4 : 0, '\0');
+    {
+      py::gil_scoped_release nogil;
+      Diag::instance().check("atomic diag", BGC_DIAG_ENTRY(bgc_diag_atomic_expected)(seed, grid, rounds, c.data(), count(c), static_cast<void*>(data.data()),
+                                                                                     data.size()));
+    }
+    return py::bytes(data);
+  }, py::arg("seed"), py::arg("grid"), py::arg("rounds"), py::arg("plants"));
+  m.def("diag_atomic_rate_expected", [](unsigned seed, int rate_grid, int rate_iters, int cls) {
+    const bool sized = rate_grid >= 8 && rate_grid <= 4096;
+    std::string data(sized ? static_cast<size_t>(rate_grid) / 8 * 4 * (cls == BGC_ATOMIC_RATE_RTN ? 1 : 4096) * 4 : 0, '\0');
+    Diag::instance().check("atomic diag", BGC_DIAG_ENTRY(bgc_diag_atomic_rate_expected)(seed, rate_grid, rate_iters, cls,
+                                                                                          reinterpret_cast<uint32_t*>(data.data()), data.size() / 4));
+    return py::bytes(data);
+  }, py::arg("seed"), py::arg("rate_grid"), py::arg("rate_iters"), py::arg("cls"));
   m.def("diag_valu_trans_ulps", [] {
     return py::make_tuple(BGC_VALU_EXP_ULPS, BGC_VALU_LOG_ULPS, BGC_VALU_RCP_ULPS, BGC_VALU_RSQ_ULPS, BGC_VALU_SQRT_ULPS);
   });
