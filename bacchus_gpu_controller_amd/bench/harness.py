@@ -487,7 +487,20 @@ def _kl_lock(info):
 
     st = requests.get(info["server"] + "/_kl/stats", timeout=10, verify=info["apiserver_verify"]).json()
     return {"total": st["store_lock"], "by_type": st.get("by_type_lock", {}), "requests": st["requests"],
-            "by_kind": st.get("requests_by_kind", {}), "store_shards": st.get("store_shards")}
+            "by_kind": st.get("requests_by_kind", {}), "store_shards": st.get("store_shards"),
+            "watch": {k: st.get("watch_" + k) for k in ("events_queued", "notifies", "batches_written")}}
+
+
+def _watch_report(s0, s1):
+    """kube-lite's watch delivery over the window: wake-ups recorded per queued event and
+    events per written batch.  None for a kube-lite without the counters (an older build
+    under BGC_BIN_DIR)."""
+    w0, w1 = s0.get("watch") or {}, s1.get("watch") or {}
+    if any(w0.get(k) is None or w1.get(k) is None for k in ("events_queued", "notifies", "batches_written")):
+        return None
+    d = {k: w1[k] - w0[k] for k in w1}
+    return dict(d, notifies_per_event=round(d["notifies"] / max(1, d["events_queued"]), 4),
+                events_per_batch=round(d["events_queued"] / max(1, d["batches_written"]), 3))
 
 
 PRODUCT = ("controller", "admission", "synchronizer", "node-agent")
@@ -644,6 +657,7 @@ def _phase(d, nat, info, args, phase, concurrency, warmup, steps, cluster):
         # test API server and load_driver the tenant simulator: neither ships.
         "cpu_ms_per_cr": cpu_ms,
         "apiserver_store_lock": _lock_report(lock0, lock1, elapsed),
+        "apiserver_watch_delivery": _watch_report(lock0, lock1),
         "apiserver_requests_per_cr": round((lock1["requests"] - lock0["requests"]) / per_cr, 2),
         "apiserver_requests_per_cr_by_kind": {
             k: round((v - lock0["by_kind"].get(k, 0)) / per_cr, 3)

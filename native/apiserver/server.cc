@@ -1,8 +1,10 @@
 #include "apiserver/server.h"
+#include "apiserver/rv_splice.h"
 
 #include <algorithm>
 #include <array>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -287,6 +289,16 @@ struct Stored {
   std::shared_ptr<const Managers> managers = no_managers();
 };
 
+// The object of a committed event line ({"type":T,"object":<obj>}\n) as that commit
+// serialized it: the same tree with the same resourceVersion digits, so the text equals
+// Stored::obj->dump().  Empty when the line is gone (null) or not of that form.
+std::string_view committed_object_text(const std::string* line) {
+  static const std::string kObjectKey = ",\"object\":";
+  const size_t at = line ? line->find(kObjectKey) : std::string::npos;
+  if (at == std::string::npos || line->size() < at + kObjectKey.size() + 2) return {};
+  return std::string_view(*line).substr(at + kObjectKey.size(), line->size() - (at + kObjectKey.size()) - 2);
+}
+
 // PartialObjectMetadata (meta.k8s.io/v1): what metadata-only clients ask for with
 // Accept: application/json;as=PartialObjectMetadata[List];g=meta.k8s.io;v=v1.
 bool wants_metadata(const http::Request& req) {
@@ -413,6 +425,20 @@ std::shared_ptr<const Value> filter_view(const Value& obj) {
   Value meta = Value::object({{"name", m.get("name")}});
   if (m.contains("labels")) meta["labels"] = m.get("labels");
   return std::make_shared<const Value>(Value::object({{"metadata", std::move(meta)}}));
+}
+
+// Queue length at which a watch writer stops waiting for its burst to grow (do_watch) and
+// at which a commit therefore wakes it (emit_locked).
+constexpr size_t kWatchBurst = 16;
+
+// Watch delivery, process-wide (exported in /_kl/stats): events pushed onto watch queues,
+// wake-ups recorded for watch writers, and batches (chunks of events) written.
+struct WatchCounters {
+  std::atomic<uint64_t> events_queued{0}, notifies{0}, batches_written{0};
+};
+inline WatchCounters& watch_counters() {
+  static WatchCounters c;
+  return c;
 }
 
 struct WatchSub {
@@ -596,6 +622,7 @@ struct TypeStore {
   }
   RwLock seq;
   std::atomic<uint64_t> version{0};                          // bumped by every commit/erase (under seq)
+  std::atomic<size_t> longest_line{1024};                    // longest committed event line (a reserve hint)
   LockStats stats;                                           // the shard locks
   LockStats seq_stats;                                       // seq (the type's commit order)
   std::deque<std::shared_ptr<const EventRec>> history;       // rv-ordered (appended under seq)
@@ -993,7 +1020,10 @@ struct ApiServer::Impl {
   // ---------------------------------------------------------------- events
   // Work moved out of the exclusive section (see prepare_commit).
   struct PreparedEvent {
-    std::string head, tail;  // event line = head + rv digits + tail
+    // The event line, whole, with the resourceVersion placeholder at [rv_at, rv_at + rv_len)
+    // between the value's quotes: commit_locked replaces it by the digits in this buffer.
+    std::string line;
+    size_t rv_at = 0, rv_len = 0;
     bool ok = false;
     // built before the exclusive section: the resuming-watch filter view and the event
     // record (its line is filled in under the lock)
@@ -1022,19 +1052,36 @@ struct ApiServer::Impl {
       st.history.pop_front();
     }
     const std::string& name = rec->meta->get("metadata").get_string("name");
+    uint64_t queued = 0, notifies = 0;
     std::lock_guard<std::mutex> wg(st.watches_mu);
     for (const auto& w : st.watches) {
       if (!w->ns.empty() && w->ns != ns) continue;
       if (!w->fields.name_ok(name)) continue;
       View view;
       if (!view_for(w->sel, *rec, &view)) continue;
+      // The writer is woken only for a change of the state its waits test (do_watch): the
+      // queue became non-empty, it reached the burst threshold, or it overflowed.  Decided
+      // under m, where the writer evaluates its predicates, so no wake-up is lost; an event
+      // in between finds the writer either busy or inside its coalescing window.
+      bool wake;
       {
         std::lock_guard<std::mutex> g(w->m);
-        if (w->q.size() > 100000) w->overflow = true;
-        else w->q.push_back({rec, view});
+        if (w->q.size() > 100000) {
+          wake = !w->overflow;
+          w->overflow = true;
+        } else {
+          w->q.push_back({rec, view});
+          ++queued;
+          wake = w->q.size() == 1 || w->q.size() == kWatchBurst;
+        }
       }
-      t_pending_wakeups.push_back(w);
+      if (wake) {
+        t_pending_wakeups.push_back(w);
+        ++notifies;
+      }
     }
+    if (queued) watch_counters().events_queued.fetch_add(queued, std::memory_order_relaxed);
+    if (notifies) watch_counters().notifies.fetch_add(notifies, std::memory_order_relaxed);
     return rec->line;
   }
 
@@ -1058,14 +1105,22 @@ struct ApiServer::Impl {
   };
   std::mutex hook_match_mu;                    // matching_webhooks' cache
   uint64_t hook_match_version = ~uint64_t{0};  // MWC store version the cache is for
-  std::unordered_map<std::string, std::vector<HookMatch>> hook_match_cache;
+  // One cache entry: the hooks, and the parts of their AdmissionReview request that depend
+  // only on the entry's key (type, subresource, operation), built once per entry.
+  struct HookSet {
+    std::vector<HookMatch> hooks;
+    std::string kinds;    // ,"kind":<gvk>,"resource":<gvr>[,"subResource":S],"requestKind":..[,"requestSubResource":S]
+    std::string op;       // ,"operation":"OP"
+    std::string options;  // ,"dryRun":false,"options":{..}}}
+  };
+  std::unordered_map<std::string, std::shared_ptr<const HookSet>> hook_match_cache;
 
   // The hooks a request triggers, cached per (type, subresource, operation) for one version
   // of the MutatingWebhookConfigurations: every UserBootstrap write asks, and scanning the
   // configurations under all their shard locks each time serialized the writers.
-  std::vector<HookMatch> matching_webhooks(const TypeInfo& ti, const std::string& sub, const std::string& op) {
+  std::shared_ptr<const HookSet> matching_webhooks(const TypeInfo& ti, const std::string& sub, const std::string& op) {
     TypeInfo* mwc = type_by_key(kube::types::MutatingWebhookConfiguration.group + "/v1/mutatingwebhookconfigurations");
-    if (!mwc) return {};
+    if (!mwc) return nullptr;
     const std::string cache_key = ti.key() + "|" + sub + "|" + op;
     {
       std::lock_guard<std::mutex> g(hook_match_mu);
@@ -1074,7 +1129,8 @@ struct ApiServer::Impl {
         if (it != hook_match_cache.end()) return it->second;
       }
     }
-    std::vector<HookMatch> out;
+    auto set = std::make_shared<HookSet>();
+    std::vector<HookMatch>& out = set->hooks;
     AllShards lk(*mwc->store, false);
     const uint64_t version = mwc->store->version.load(std::memory_order_acquire);  // no commit in flight
     std::string res = ti.rt.plural + (sub.empty() ? "" : "/" + sub);
@@ -1104,15 +1160,29 @@ struct ApiServer::Impl {
         }
       }
     }
+    if (!out.empty()) {
+      const std::string gvk = "{\"group\":" + json::quote(ti.rt.group) + ",\"version\":" + json::quote(ti.rt.version) +
+                              ",\"kind\":" + json::quote(ti.rt.kind) + "}";
+      const std::string gvr = "{\"group\":" + json::quote(ti.rt.group) + ",\"version\":" + json::quote(ti.rt.version) +
+                              ",\"resource\":" + json::quote(ti.rt.plural) + "}";
+      set->kinds = ",\"kind\":" + gvk + ",\"resource\":" + gvr;
+      if (!sub.empty()) set->kinds += ",\"subResource\":" + json::quote(sub);
+      set->kinds += ",\"requestKind\":" + gvk + ",\"requestResource\":" + gvr;
+      if (!sub.empty()) set->kinds += ",\"requestSubResource\":" + json::quote(sub);
+      set->op = ",\"operation\":" + json::quote(op);
+      const char* opts_kind = op == "CREATE" ? "CreateOptions" : op == "DELETE" ? "DeleteOptions" : "UpdateOptions";
+      set->options = std::string(",\"dryRun\":false,\"options\":{\"kind\":") + json::quote(opts_kind) +
+                     ",\"apiVersion\":\"meta.k8s.io/v1\"}}}";
+    }
     {
       std::lock_guard<std::mutex> g(hook_match_mu);
       if (hook_match_version != version) {
         hook_match_cache.clear();
         hook_match_version = version;
       }
-      hook_match_cache[cache_key] = out;
+      hook_match_cache[cache_key] = set;
     }
-    return out;
+    return set;
   }
 
   // Per-hook client cache keyed by the hook's address inside its (immutable, kept-alive)
@@ -1171,9 +1241,17 @@ struct ApiServer::Impl {
 
   // Runs mutating webhooks; may modify `obj`. Throws StatusError on deny/failure.
   void call_webhooks(const TypeInfo& ti, const std::string& sub, const std::string& op, const std::string& ns,
-                     const std::string& name, Value* obj, const Value* old, const UserInfo& user) {
-    auto hooks = matching_webhooks(ti, sub, op);
-    if (hooks.empty()) return;
+                     const std::string& name, Value* obj, const Stored* old_stored, const UserInfo& user) {
+    const std::shared_ptr<const HookSet> set = matching_webhooks(ti, sub, op);
+    if (!set || set->hooks.empty()) return;
+    const Value* old = old_stored ? old_stored->obj.get() : nullptr;
+    // oldObject is the stored object as its commit serialized it, while the watch history
+    // still holds that event line (erase_locked reuses it the same way); else it is dumped.
+    const std::shared_ptr<const std::string> old_line = old_stored ? old_stored->line.lock() : nullptr;
+    const std::string_view old_text = committed_object_text(old_line.get());
+#ifdef BGC_DEBUG_CHECKS  // Debug and sanitizer builds (the Release flags leave assert() on)
+    assert(old_text.empty() || old_text == old->dump());
+#endif
     static auto& hist = metrics::Registry::global().histogram("kl_webhook_duration_seconds", "Webhook callout latency");
     static auto& calls = metrics::Registry::global().counter("kl_webhook_calls_total", "Webhook callouts (any outcome)");
     static auto& ring = [] () -> metrics::SampleLog& {
@@ -1181,39 +1259,37 @@ struct ApiServer::Impl {
       r.link("kl_webhook_calls_total", &calls);  // counted with the sample, under its lock
       return r;
     }();
-    for (const auto& hm : hooks) {
+    for (const auto& hm : set->hooks) {
       const Value& hook = *hm.hook;
       std::string fail_policy = hook.get_string("failurePolicy", "Fail");
       int timeout_s = hook.get("timeoutSeconds").is_int() ? static_cast<int>(hook.get("timeoutSeconds").as_int()) : 10;
       std::string uid = crypto::uuid_v4();
       // AdmissionReview serialized in place: object/oldObject are dumped straight from the
       // caller's trees instead of being deep-copied into a request Value first.
-      const std::string opts_kind = op == "CREATE" ? "CreateOptions" : op == "DELETE" ? "DeleteOptions" : "UpdateOptions";
-      const std::string gvk = "{\"group\":" + json::quote(ti.rt.group) + ",\"version\":" + json::quote(ti.rt.version) +
-                              ",\"kind\":" + json::quote(ti.rt.kind) + "}";
-      const std::string gvr = "{\"group\":" + json::quote(ti.rt.group) + ",\"version\":" + json::quote(ti.rt.version) +
-                              ",\"resource\":" + json::quote(ti.rt.plural) + "}";
-      std::string body;
-      body.reserve(1024 + (obj ? 2048 : 0) + (old ? 2048 : 0));
+      // The body is built in a buffer this thread keeps (capacity and all) from call to call.
+      thread_local std::string body;
+      body.clear();
+      body.reserve(1024 + (obj ? 2048 : 0) + (old ? std::max<size_t>(2048, old_text.size()) : 0));
       body += "{\"kind\":\"AdmissionReview\",\"apiVersion\":\"admission.k8s.io/v1\",\"request\":{\"uid\":";
       body += json::quote(uid);
-      body += ",\"kind\":" + gvk + ",\"resource\":" + gvr;
-      if (!sub.empty()) body += ",\"subResource\":" + json::quote(sub);
-      body += ",\"requestKind\":" + gvk + ",\"requestResource\":" + gvr;
-      if (!sub.empty()) body += ",\"requestSubResource\":" + json::quote(sub);
-      body += ",\"name\":" + json::quote(name);
-      if (!ns.empty()) body += ",\"namespace\":" + json::quote(ns);
-      body += ",\"operation\":" + json::quote(op);
+      body += set->kinds;
+      body += ",\"name\":";
+      body += json::quote(name);
+      if (!ns.empty()) {
+        body += ",\"namespace\":";
+        body += json::quote(ns);
+      }
+      body += set->op;
       body += ",\"userInfo\":";
       user.to_json().dump_to(body);
       body += ",\"object\":";
       if (obj) obj->dump_to(body);
       else body += "null";
       body += ",\"oldObject\":";
-      if (old) old->dump_to(body);
-      else body += "null";
-      body += ",\"dryRun\":false,\"options\":{\"kind\":" + json::quote(opts_kind) +
-              ",\"apiVersion\":\"meta.k8s.io/v1\"}}}";
+      if (!old) body += "null";
+      else if (!old_text.empty()) body.append(old_text.data(), old_text.size());
+      else old->dump_to(body);
+      body += set->options;
       std::string err;
       Value resp_review;
       int64_t t0 = metrics::now_ns();
@@ -1233,6 +1309,7 @@ struct ApiServer::Impl {
       } catch (const std::exception& e) {
         err = e.what();
       }
+      if (body.capacity() > (256u << 10)) std::string().swap(body);  // one huge object: not kept per thread
       double secs = static_cast<double>(metrics::now_ns() - t0) * 1e-9;
       hist.observe(secs);
       ring.add(secs, &calls);
@@ -1505,22 +1582,38 @@ struct ApiServer::Impl {
     static const std::string p = "\x01rv\x01";
     return p;
   }
-  static PreparedEvent prepare_commit(Value& obj, const Managers& managers, const std::string& api_version,
-                                      const char* type) {
+  // `prev_line_size`: the size of the object's previous event line when the caller holds
+  // it, else 0 (the type's longest line so far is the hint, up to kLineHintMax: one large
+  // object must not make every later small one reserve its size): the buffer is reserved
+  // once, with room for the longest resourceVersion, instead of growing through the dump.
+  static constexpr size_t kLineHintMax = 8192;
+  static PreparedEvent prepare_commit(const TypeInfo& ti, Value& obj, const Managers& managers, const char* type,
+                                      size_t prev_line_size = 0) {
     obj["metadata"]["resourceVersion"] = rv_placeholder();
-    render_managed(obj, managers, api_version);
-    std::string line = std::string("{\"type\":\"") + type + "\",\"object\":";
+    render_managed(obj, managers, ti.rt.api_version());
+    static const std::string kKey = "\"resourceVersion\":\"";
+    static const std::string needle = "\"resourceVersion\":" + Value(rv_placeholder()).dump();
+    std::atomic<size_t>& longest = ti.store->longest_line;
+    const size_t hint =
+        prev_line_size ? prev_line_size + 256 : std::min(longest.load(std::memory_order_relaxed), kLineHintMax);
+    PreparedEvent pe;
+    std::string& line = pe.line;
+    line.reserve(hint + kRvSpliceSlack);
+    line += "{\"type\":\"";
+    line += type;
+    line += "\",\"object\":";
     obj.dump_to(line);
     line += "}\n";
-    static const std::string needle = "\"resourceVersion\":" + Value(rv_placeholder()).dump();
-    PreparedEvent pe;
+    if (line.size() > longest.load(std::memory_order_relaxed)) longest.store(line.size(), std::memory_order_relaxed);
+    // the watch history keeps this buffer: a hint far beyond the line (at most kLineHintMax
+    // for a new object, so a small copy) does not stay allocated with the event
+    if (line.capacity() > line.size() + line.size() / 2 + 512) line.shrink_to_fit();
     pe.filter = filter_view(obj);
     pe.rec = std::make_shared<EventRec>();
     size_t pos = line.find(needle);
     if (pos == std::string::npos) return pe;
-    pe.head.assign(line, 0, pos);
-    pe.head += "\"resourceVersion\":\"";
-    pe.tail.assign(line, pos + needle.size() - 1, std::string::npos);  // from the closing quote
+    pe.rv_at = pos + kKey.size();
+    pe.rv_len = needle.size() - kKey.size() - 1;  // up to the closing quote
     pe.ok = true;
     return pe;
   }
@@ -1531,12 +1624,12 @@ struct ApiServer::Impl {
   // deleted object.
   std::shared_ptr<const Value> commit_locked(const TypeInfo& ti, const std::string& ns, const std::string& name,
                                             Value obj, Managers managers, const Stored* prev,
-                                            const PreparedEvent* pe = nullptr, bool* dangling = nullptr,
+                                            PreparedEvent* pe = nullptr, bool* dangling = nullptr,
                                             std::shared_ptr<const std::string>* line_out = nullptr) {
     TypeStore& ts = *ti.store;
     PreparedEvent local;
     if (!pe || !pe->ok) {
-      local = prepare_commit(obj, managers, ti.rt.api_version(), prev ? "MODIFIED" : "ADDED");
+      local = prepare_commit(ti, obj, managers, prev ? "MODIFIED" : "ADDED");
       pe = &local;
     }
     std::string key = obj_key(ti.rt, ns, name);
@@ -1584,10 +1677,8 @@ struct ApiServer::Impl {
       digits = rv_str(new_rv);
       std::string preline;
       if (pe->ok) {
-        preline.reserve(pe->head.size() + digits.size() + pe->tail.size());
-        preline += pe->head;
-        preline += digits;
-        preline += pe->tail;
+        preline = std::move(pe->line);
+        splice_rv(preline, pe->rv_at, pe->rv_len, digits);
       } else {  // no resourceVersion placeholder found (never for a prepared object)
         obj["metadata"]["resourceVersion"] = digits;
         preline = std::string("{\"type\":\"") + (prev ? "MODIFIED" : "ADDED") + "\",\"object\":";
@@ -1628,19 +1719,16 @@ struct ApiServer::Impl {
     // The DELETED event carries the object at the new resourceVersion: its serialization is
     // split around the stored resourceVersion and the new digits are spliced in under seq.
     std::shared_ptr<const Value> ptr = it->second.obj;
-    std::string line = "{\"type\":\"DELETED\",\"object\":";
-    const size_t obj_at = line.size();
-    static const std::string kObjectKey = ",\"object\":";
     const std::shared_ptr<const std::string> held = it->second.line.lock();
-    const std::string* committed = held.get();
-    const size_t at = committed ? committed->find(kObjectKey) : std::string::npos;
-    if (at != std::string::npos && committed->size() >= at + kObjectKey.size() + 2) {
-      // the object as its last commit serialized it (same tree, same rv digits)
-      line.append(*committed, at + kObjectKey.size(), committed->size() - (at + kObjectKey.size()) - 2);
-    } else {
-      ptr->dump_to(line);
-    }
+    const std::string_view committed = committed_object_text(held.get());
+    std::string line;
+    line.reserve((held ? held->size() : ts.longest_line.load(std::memory_order_relaxed)) + 8 + kRvSpliceSlack);
+    line += "{\"type\":\"DELETED\",\"object\":";
+    const size_t obj_at = line.size();
+    if (!committed.empty()) line.append(committed.data(), committed.size());
+    else ptr->dump_to(line);
     line += "}\n";
+    static const std::string kRvKey = "\"resourceVersion\":\"";
     const std::string old_rv = "\"resourceVersion\":" + json::quote(ptr->get("metadata").get_string("resourceVersion"));
     const size_t pos = line.find(old_rv, obj_at);
     auto filter = filter_view(*ptr);
@@ -1666,7 +1754,8 @@ struct ApiServer::Impl {
       new_rv = ++rv;
       const std::string digits = rv_str(new_rv);
       if (pos != std::string::npos) {
-        line.replace(pos, old_rv.size(), "\"resourceVersion\":\"" + digits + "\"");
+        // the digits alone, in place (json::quote adds nothing to digits but the two quotes)
+        splice_rv(line, pos + kRvKey.size(), old_rv.size() - kRvKey.size() - 1, digits);
       } else {  // no resourceVersion in the stored object (never for committed objects)
         Value final_obj = *ptr;
         final_obj["metadata"]["resourceVersion"] = digits;
@@ -1812,7 +1901,7 @@ struct ApiServer::Impl {
         return {cur_copy.obj, 200, nullptr};
       }
       trace_step(name, ".hook0");
-      call_webhooks(ti, sub, op, ns, name, &obj, exists ? cur_copy.obj.get() : nullptr, user);
+      call_webhooks(ti, sub, op, ns, name, &obj, exists ? &cur_copy : nullptr, user);
       trace_step(name, ".hook1");
       // identity fields cannot be changed by mutation
       obj["metadata"]["name"] = name;
@@ -1830,7 +1919,11 @@ struct ApiServer::Impl {
                           : 1;
         obj["metadata"]["generation"] = gen + 1;
       }
-      PreparedEvent pe = prepare_commit(obj, managers, ti.rt.api_version(), exists ? "MODIFIED" : "ADDED");
+      size_t prev_line_size = 0;
+      if (exists) {
+        if (const auto prev_line = cur_copy.line.lock()) prev_line_size = prev_line->size();
+      }
+      PreparedEvent pe = prepare_commit(ti, obj, managers, exists ? "MODIFIED" : "ADDED", prev_line_size);
       StoreLock lk(sh.mu, ti.store->stats);
       auto it = sh.objs.find(key);
       bool now_exists = it != sh.objs.end();
@@ -2130,17 +2223,17 @@ struct ApiServer::Impl {
   }
 
   void do_delete(ParsedPath& p, const http::Request& req, const UserInfo& user, http::ResponseWriter& w) {
-    std::shared_ptr<const Value> cur;
+    Stored cur;  // with its committed line: the webhooks' oldObject is taken from it
     const std::string key = obj_key(p.ti->rt, p.ns, p.name);
     auto& sh = p.ti->store->shard(key);
     {
       SharedStoreLock lk(sh.mu, p.ti->store->stats);
       auto it = sh.objs.find(key);
       if (it == sh.objs.end()) throw not_found(p.ti->rt, p.name);
-      cur = it->second.obj;
+      cur = it->second;
     }
     trace_step(p.name, ".hook0");
-    call_webhooks(*p.ti, "", "DELETE", p.ns, p.name, nullptr, cur.get(), user);
+    call_webhooks(*p.ti, "", "DELETE", p.ns, p.name, nullptr, &cur, user);
     trace_step(p.name, ".hook1");
     StoreLock lk(sh.mu, p.ti->store->stats);
     auto it = sh.objs.find(key);
@@ -2385,17 +2478,34 @@ struct ApiServer::Impl {
     }
     auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(timeout_s);
     auto next_bookmark = std::chrono::steady_clock::now() + std::chrono::milliseconds(opts.bookmark_interval_ms);
+    // One batch is one chunk, framed once in a buffer that keeps its capacity across batches.
+    std::string buf;
+    std::vector<QueuedEvent> batch;
+    auto frame = [&](const std::vector<QueuedEvent>& events) {
+      size_t need = http::ResponseWriter::kChunkHeaderRoom + 2;
+      for (auto& q : events) need += q.e->line_as(q.view, meta_only).size();
+      buf.clear();
+      buf.reserve(need);
+      buf.append(http::ResponseWriter::kChunkHeaderRoom, ' ');
+      for (auto& q : events) buf += q.e->line_as(q.view, meta_only);
+      watch_counters().batches_written.fetch_add(1, std::memory_order_relaxed);
+    };
+    // a backlog's buffers are not kept for the rest of the watch
+    auto written = [&] {
+      if (buf.capacity() > (1u << 20)) std::string().swap(buf);
+    };
     while (ok && !w.stopping()) {
-      std::vector<QueuedEvent> batch;
+      if (batch.capacity() > 4096) std::vector<QueuedEvent>().swap(batch);
+      else batch.clear();
       bool closed = false, overflow = false;
       {
         std::unique_lock<std::mutex> lk(sub.m);
         sub.cv.wait_for(lk, std::chrono::milliseconds(500), [&] { return !sub.q.empty() || sub.closed || sub.overflow; });
         const int coalesce_us = watch_coalesce_us.load(std::memory_order_relaxed);
-        if (coalesce_us > 0 && !sub.q.empty() && sub.q.size() < 16 && !sub.closed) {
+        if (coalesce_us > 0 && !sub.q.empty() && sub.q.size() < kWatchBurst && !sub.closed) {
           // let a burst accumulate into one write (see Options::watch_coalesce_us)
           sub.cv.wait_for(lk, std::chrono::microseconds(coalesce_us),
-                          [&] { return sub.q.size() >= 16 || sub.closed || sub.overflow; });
+                          [&] { return sub.q.size() >= kWatchBurst || sub.closed || sub.overflow; });
         }
         batch.assign(sub.q.begin(), sub.q.end());
         sub.q.clear();
@@ -2403,15 +2513,15 @@ struct ApiServer::Impl {
         overflow = sub.overflow;
       }
       if (!batch.empty()) {
-        std::string buf;
-        for (auto& q : batch) buf += q.e->line_as(q.view, meta_only);
+        frame(batch);
         const bool traced = trace::armed();
         if (traced) {  // before the write: causally before the watcher's own marks
           for (auto& q : batch) trace::mark(q.e->meta->get("metadata").get_string("name"), trace_watch);
         }
         const int64_t w0 = metrics::now_ns();
-        if (!w.write_chunk(buf)) break;
+        if (!w.write_framed_chunk(buf)) break;
         const int64_t w1 = metrics::now_ns();
+        written();
         stall::note_slow(slow_write, w0, w1);
         if (traced) {
           for (auto& q : batch) trace::mark_at(q.e->meta->get("metadata").get_string("name"), trace_written, w1);
@@ -2433,9 +2543,9 @@ struct ApiServer::Impl {
           sub.q.clear();
         }
         if (!pending.empty()) {
-          std::string buf;
-          for (auto& q : pending) buf += q.e->line_as(q.view, meta_only);
-          if (!w.write_chunk(buf)) break;
+          frame(pending);
+          if (!w.write_framed_chunk(buf)) break;
+          written();
         }
         Value bm = Value::object({{"type", "BOOKMARK"},
                                   {"object", Value::object({{"kind", p.ti->rt.kind},
@@ -2509,6 +2619,7 @@ struct ApiServer::Impl {
       return inner_.start_chunked(status, content_type);
     }
     bool write_chunk(const std::string& data) override { return inner_.write_chunk(data); }
+    bool write_framed_chunk(std::string& buf) override { return inner_.write_framed_chunk(buf); }
     void end_chunked() override { inner_.end_chunked(); }
     void abort() override { inner_.abort(); }
     bool peer_closed() override { return inner_.peer_closed(); }
@@ -2713,6 +2824,9 @@ struct ApiServer::Impl {
                                       {"resource_version", rv_str(rv.load())},
                                       {"gc_collected", static_cast<unsigned long long>(gc_collected.load())},
                                       {"store_shards", static_cast<unsigned long long>(opts.store_shards)},
+                                      {"watch_events_queued", static_cast<unsigned long long>(watch_counters().events_queued.load())},
+                                      {"watch_notifies", static_cast<unsigned long long>(watch_counters().notifies.load())},
+                                      {"watch_batches_written", static_cast<unsigned long long>(watch_counters().batches_written.load())},
                                       {"gc_pending", static_cast<unsigned long long>([&] {
                                          std::lock_guard<std::mutex> g(gc_mu);
                                          return gc_queue.size();

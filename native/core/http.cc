@@ -392,6 +392,16 @@ bool ResponseWriter::write_chunk(const std::string& data) {
   return s_->write_all(out);
 }
 
+bool ResponseWriter::write_framed_chunk(std::string& buf) {
+  if (buf.size() <= kChunkHeaderRoom) return true;
+  const size_t len = buf.size() - kChunkHeaderRoom;
+  char hdr[32];
+  const size_t n = static_cast<size_t>(std::snprintf(hdr, sizeof(hdr), "%zx\r\n", len));  // <= kChunkHeaderRoom
+  std::memcpy(&buf[kChunkHeaderRoom - n], hdr, n);
+  buf.append("\r\n", 2);
+  return s_->write_all(buf.data() + (kChunkHeaderRoom - n), n + len + 2);
+}
+
 void ResponseWriter::end_chunked() {
   if (chunked_) s_->write_all("0\r\n\r\n", 5);
 }
@@ -630,6 +640,10 @@ class H2ResponseWriter final : public ResponseWriter {
     return c_->send_headers(*st_, head(status, content_type, nullptr), false);
   }
   bool write_chunk(const std::string& data) override { return data.empty() || c_->send_data(*st_, data, false); }
+  bool write_framed_chunk(std::string& buf) override {
+    return buf.size() <= kChunkHeaderRoom ||
+           c_->send_data(*st_, std::string_view(buf).substr(kChunkHeaderRoom), false);
+  }
   void end_chunked() override {
     if (chunked_) c_->send_data(*st_, {}, true);
   }

@@ -118,6 +118,13 @@ class ResponseWriter {
   // Streaming (chunked) responses for WATCH.
   virtual bool start_chunked(int status, const std::string& content_type);
   virtual bool write_chunk(const std::string& data);
+  // A chunk from a buffer its caller framed: the first kChunkHeaderRoom bytes of `buf` are
+  // the caller's reserved room, the data follows.  The HTTP/1.1 writer puts the chunk-size
+  // line at the end of that room and the closing CRLF behind the data, so the chunk leaves
+  // in one write without a second copy (the same bytes write_chunk sends).  `buf` is the
+  // caller's to clear and reuse afterwards; its content is unspecified.
+  static constexpr size_t kChunkHeaderRoom = 18;  // 16 hex digits + CRLF
+  virtual bool write_framed_chunk(std::string& buf);
   virtual void end_chunked();
   // Drops the connection without a response (fault injection: connection reset); over
   // HTTP/2 only the request's stream is reset.
