@@ -1,4 +1,4 @@
-"""HIP/CDNA4 GPU health kernels (native/gpu/hip/: hbm.hip, mfma.hip, lds.hip, cache.hip, valu.hip, atomic.hip, gemm_soak.hip) exposed to Python.
+"""HIP/CDNA4 GPU health kernels (native/gpu/hip/: hbm.hip, mfma.hip, lds.hip, cache.hip, valu.hip, atomic.hip, regfile.hip, gemm_soak.hip) exposed to Python.
 
 These are the only compute kernels in the framework: the reference controller has none
 (SURVEY §2.5).  They back the node agent's diagnostics before a GPU is advertised
@@ -20,6 +20,8 @@ These are the only compute kernels in the framework: the reference controller ha
   instructions on every SIMD, refereed by the host CPU and attributed to CU, SIMD and lane; then the vector rates
 * ``atomic(device)``    — every global and LDS atomic form (integer, 64-bit, fp32, fp64, packed bf16 / fp16 adds, compare-and-swap,
   returning adds as tickets) in a table per workgroup and in one shared by the launch, refereed by the host CPU; then the atomic rates
+* ``regfile(device)``   — a march of every SIMD's whole vector register file (512 registers a lane, 128 KiB a SIMD) in two
+  layouts, attributed to CU, SIMD, register and lane; then a rotate of 504 registers, a moving-data check and the move rate
 * ``gemm_check(device)``— a bf16 GEMM on the matrix cores checked element by element against
   a double-precision product of the same operands on the host
 * ``gemm_soak(device)`` — the sustained-throughput soak: the 8-phase ping-pong GEMM
@@ -34,11 +36,11 @@ These are the only compute kernels in the framework: the reference controller ha
 * ``pcie(device)``      — host<->device copy bandwidth, pinned
 * ``device_bdf(device)``— the HIP device's PCI address, to match it to amdsmi / kubelet
 * ``hbm_planted``, ``hbm_walk_planted``, ``pcie_planted``, ``mfma_planted``,
-  ``mfma_lowp_planted``, ``mfma_classic_planted``, ``lds_planted``, ``cache_planted``, ``valu_planted``, ``atomic_planted``, ``gemm_soak_planted``, ``burn_planted`` — for tests: the same diagnostics with wrong
+  ``mfma_lowp_planted``, ``mfma_classic_planted``, ``lds_planted``, ``cache_planted``, ``valu_planted``, ``atomic_planted``, ``regfile_planted``, ``gemm_soak_planted``, ``burn_planted`` — for tests: the same diagnostics with wrong
   values planted in their own data, to show that they are detected (see below)
-* ``mfma_delayed``, ``burn_delayed``, ``cache_delayed``, ``valu_delayed``, ``atomic_delayed`` — for tests: the matrix-core throughput, the burn, the L2 rate, the vector and the atomic rates with
+* ``mfma_delayed``, ``burn_delayed``, ``cache_delayed``, ``valu_delayed``, ``atomic_delayed``, ``regfile_delayed`` — for tests: the matrix-core throughput, the burn, the L2 rate, the vector and the atomic rates with
   chosen waves, launches or workgroups made slow by a known time, to show that it reaches the rates
-* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile``, ``mfma_classic_tile``, ``lds_data``, ``cache_data``, ``valu_data``, ``valu_expected``, ``atomic_data``, ``atomic_expected``, ``atomic_rate_expected`` — for tests:
+* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile``, ``mfma_classic_tile``, ``lds_data``, ``cache_data``, ``valu_data``, ``valu_expected``, ``atomic_data``, ``atomic_expected``, ``atomic_rate_expected``, ``regfile_data``, ``regfile_expected``, ``regfile_layout`` — for tests:
   the same diagnostics, returning the data they generated for themselves (see below)
 
 All fail loudly (RuntimeError) if ``libbgc_gpu_diag.so`` or the GPU is missing; there
@@ -195,6 +197,25 @@ def atomic(device=0, wgs_per_cu=ATOMIC_WGS_PER_CU, rounds=ATOMIC_ROUNDS, rate_it
     return json.loads(native().diag_atomic(device, wgs_per_cu, rounds, rate_iters, seed))
 
 
+REGFILE_REGS = 512  # of a lane: v0..v255 are 0..255, a0..a255 are 256..511
+REGFILE_PHASES = ("layout0_pass0", "layout0_pass1", "layout1_pass0", "layout1_pass1", "rotate")  # a plant's or a dump's phase, 0..4
+REGFILE_ROTATE = 4
+REGFILE_PLANT_REGS = (0, 5, 128, 250, 255, 256, 384, 511)  # BGC_REGFILE_PLANT_REGS: the register of a plant's slot
+# Defaults of regfile(): every SIMD is marched twice, by waves of different seeds, and the rotate runs long enough for
+# the launch to outlast its ramp (profiles/regfile_diag/rates.json).
+REGFILE_WGS_PER_CU = 2
+REGFILE_SWEEPS = 4096
+
+
+def regfile(device=0, wgs_per_cu=REGFILE_WGS_PER_CU, sweeps=REGFILE_SWEEPS, seed=0x5EED):
+    """The vector register file as a memory: cus * `wgs_per_cu` (1..8) workgroups whose four waves each hold a SIMD's whole file
+    (512 registers a lane) march it with a per-wave pattern and its inverse in two layouts that together cover every register
+    (``vgpr_mismatches``, ``agpr_mismatches``), then rotate a ring of 504 registers by one place `sweeps` (1..65536) times and
+    verify where every word arrived (``rotate_mismatches``, ``rate_ok``): ``mov_tops`` is 10^12 lane-moves per second.  A wrong
+    word names its CU, SIMD, register (``first_bad_reg`` 0..511, ``first_bad_reg_name``), lane and phase."""
+    return json.loads(native().diag_regfile(device, wgs_per_cu, sweeps, seed))
+
+
 def gemm_check(device=0, m=4096, n=4096, k=4096, seed=0x5EED):
     return json.loads(native().diag_gemm_check(device, m, n, k, seed))
 
@@ -319,6 +340,20 @@ def atomic_delayed(delays, device=0, wgs_per_cu=1, rounds=2, rate_iters=15, seed
 
 
 MAX_DELAY_TICKS = 10_000_000  # 100 ms of the 100 MHz constant clock
+
+
+def regfile_planted(plants, device=0, wgs_per_cu=1, sweeps=3, seed=0x5EED):
+    """`plants` = [(wave or ALL_WAVES, phase 0..4, slot of REGFILE_PLANT_REGS, lane, xor mask), ...]: that register of that lane
+    is XORed with the mask after the fill of that phase and before its verify; in the rotate (phase 4) before the sweeps.  The
+    phase must hold a pattern in the register: a layout's own eight (``regfile_layout()``) are refused."""
+    return json.loads(native().diag_regfile_planted(device, wgs_per_cu, sweeps, seed, [tuple(p) for p in plants]))
+
+
+def regfile_delayed(delays, device=0, wgs_per_cu=1, sweeps=64, seed=0x5EED):
+    """`delays` = [(wave or ALL_WAVES, ticks), ...]: in the timed rotate launch that wave waits `ticks` of the 100 MHz constant
+    clock after its loop and before it reads its end time.  No value is touched; the time shows in mov_tops, rotate_ms,
+    slowest_cu_key, slowest_simd and simd_balance."""
+    return json.loads(native().diag_regfile_delayed(device, wgs_per_cu, sweeps, seed, [tuple(d) for d in delays]))
 
 
 def valu_delayed(delays, device=0, waves_per_simd=1, rounds=2, rate_iters=16, seed=0x5EED):
@@ -515,6 +550,37 @@ def atomic_rate_expected(rate_grid, rate_iters, cls, seed=0x5EED):
     code = _valu_code(ATOMIC_RATE_CLASSES, cls)
     out = np.frombuffer(native().diag_atomic_rate_expected(seed, rate_grid, rate_iters, code), dtype="<u4")
     return out if code == 3 else out.reshape(-1, 64, 64)
+
+
+REGFILE_LAYOUT = np.dtype([("regs", "<i4"), ("lanes", "<i4"), ("temps", "<i4"), ("ring_regs", "<i4"), ("plant_slots", "<i4"),
+                           ("marched", "u1", (2, 512)), ("temp_regs", "<i4", (2, 8)), ("ring", "<i4", 512), ("plant_regs", "<i4", 8),
+                           ("plant_phase_ok", "u1", (8, 5))])  # bgc_regfile_layout
+REGFILE_PLACE = np.dtype([("cu_key", "<i4"), ("simd", "<i4")])  # bgc_regfile_place
+
+
+def regfile_layout():
+    """The two march layouts, the rotate's ring and the plant registers (bgc_regfile_layout), as a numpy record: ``marched``
+    [layout, register], ``temp_regs`` [layout], ``ring`` (its first ``ring_regs`` entries: ring index -> register),
+    ``plant_regs`` [slot] and ``plant_phase_ok`` [slot, phase].  Needs no GPU."""
+    return np.frombuffer(native().diag_regfile_layout(), dtype=REGFILE_LAYOUT)[0]
+
+
+def regfile_data(wave, phase, plants=(), delays=(), device=0, wgs_per_cu=1, sweeps=3, seed=0x5EED):
+    """(result, words, march_places, rotate_places) of a run with the plants of regfile_planted and the delays of regfile_delayed:
+    wave `wave`'s whole file as phase `phase` had it, [register, lane] uint32 (after the fill and the plants of a march phase,
+    or after the timed rotate's sweeps; the phase's own eight registers are 0), and the (``cu_key``, ``simd``) every wave
+    recorded in the march launch and in the timed rotate launch of this very run."""
+    r, words, march, rotate = native().diag_regfile_data(device, wgs_per_cu, sweeps, seed, wave, phase, [tuple(p) for p in plants],
+                                                         [tuple(d) for d in delays])
+    return (json.loads(r), np.frombuffer(words, dtype="<u4").reshape(REGFILE_REGS, 64), np.frombuffer(march, dtype=REGFILE_PLACE),
+            np.frombuffer(rotate, dtype=REGFILE_PLACE))
+
+
+def regfile_expected(wave, phase, sweeps=3, plants=(), seed=0x5EED):
+    """What regfile_data returns as `words` for that wave, phase, sweep count and plants, from the host reference
+    (regfile_ref.h): after `sweeps` sweeps ring index i holds what the fill and the plants put at index (i + sweeps) mod
+    ring_regs.  Needs no GPU."""
+    return np.frombuffer(native().diag_regfile_expected(seed, wave, phase, sweeps, [tuple(p) for p in plants]), dtype="<u4").reshape(REGFILE_REGS, 64)
 
 
 def _bf16_bytes(x):

@@ -349,6 +349,46 @@ json::Value to_json(int device, const bgc_atomic_result& r) {
                               {"passed", clean && r.tickets_out_of_range == 0 && r.rate_ok != 0}});
 }
 
+json::Value to_json(int device, const bgc_regfile_result& r) {
+  static const char* const kPhases[BGC_REGFILE_PHASES] = {"layout0_pass0", "layout0_pass1", "layout1_pass0", "layout1_pass1", "rotate"};
+  char bits[16], lanes[24], reg[8] = "";
+  std::snprintf(bits, sizeof(bits), "0x%08x", r.bad_bits);
+  std::snprintf(lanes, sizeof(lanes), "0x%016llx", static_cast<unsigned long long>(r.bad_lane_mask));
+  const bool clean = r.mismatches == 0;
+  if (!clean) std::snprintf(reg, sizeof(reg), "%c%d", r.first_bad_reg < 256 ? 'v' : 'a', r.first_bad_reg % 256);
+  return json::Value::object({{"device", device},
+                              {"cus", r.cus},
+                              {"cus_seen", r.cus_seen},
+                              {"simds", r.simds},
+                              {"simds_seen", r.simds_seen},
+                              {"regs_marched", r.regs_marched},
+                              {"ring_regs", r.ring_regs},
+                              {"words_checked", static_cast<unsigned long long>(r.words_checked)},
+                              {"mismatches", static_cast<unsigned long long>(r.mismatches)},
+                              {"vgpr_mismatches", static_cast<unsigned long long>(r.vgpr_mismatches)},
+                              {"agpr_mismatches", static_cast<unsigned long long>(r.agpr_mismatches)},
+                              {"rotate_mismatches", static_cast<unsigned long long>(r.rotate_mismatches)},
+                              {"bad_simds", r.bad_simds},
+                              {"bad_bits", clean ? json::Value() : json::Value(std::string(bits))},
+                              {"bad_lane_mask", clean ? json::Value() : json::Value(std::string(lanes))},
+                              {"first_bad_cu_key", clean ? json::Value() : json::Value(r.first_bad_cu_key)},
+                              {"first_bad_simd", clean ? json::Value() : json::Value(r.first_bad_simd)},
+                              {"first_bad_reg", clean ? json::Value() : json::Value(r.first_bad_reg)},  // 0..511: v0..v255, a0..a255
+                              {"first_bad_reg_name", clean ? json::Value() : json::Value(std::string(reg))},
+                              {"first_bad_lane", clean ? json::Value() : json::Value(r.first_bad_lane)},
+                              {"first_bad_phase", clean ? json::Value() : json::Value(r.first_bad_phase)},
+                              {"first_bad_phase_name", clean ? json::Value() : json::Value(std::string(kPhases[r.first_bad_phase]))},
+                              {"mov_tops", r.mov_tops},
+                              {"rate_ok", r.rate_ok != 0},
+                              {"simd_balance", r.simd_balance},
+                              {"slowest_cu_key", r.slowest_cu_key},
+                              {"slowest_simd", r.slowest_simd},
+                              {"march_ms", r.march_ms},
+                              {"rotate_ms", r.rotate_ms},
+                              {"elapsed_ms", r.elapsed_ms},
+                              {"passed", clean && r.rate_ok != 0 && r.simds_seen == r.simds}});
+}
+
 json::Value to_json(int device, const bgc_pcie_result& r) {
   return json::Value::object({{"device", device}, {"bytes", static_cast<unsigned long long>(r.bytes)},
                               {"iters", r.iters}, {"h2d_gbps", r.h2d_gbps}, {"d2h_gbps", r.d2h_gbps},
@@ -420,6 +460,10 @@ json::Value Diag::valu(int device, int waves_per_simd, int rounds, int rate_iter
 
 json::Value Diag::atomic(int device, int wgs_per_cu, int rounds, int rate_iters, uint32_t seed) {
   return call("atomic diag", atomic_, device, wgs_per_cu, rounds, rate_iters, seed);
+}
+
+json::Value Diag::regfile(int device, int wgs_per_cu, int sweeps, uint32_t seed) {
+  return call("regfile diag", regfile_, device, wgs_per_cu, sweeps, seed);
 }
 
 json::Value Diag::pcie(int device, uint64_t bytes, int iters, uint32_t seed) {

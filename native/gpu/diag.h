@@ -102,6 +102,7 @@ json::Value to_json(int device, const bgc_lds_result& r);
 json::Value to_json(int device, const bgc_cache_result& r);
 json::Value to_json(int device, const bgc_valu_result& r);
 json::Value to_json(int device, const bgc_atomic_result& r);
+json::Value to_json(int device, const bgc_regfile_result& r);
 json::Value to_json(int device, const bgc_pcie_result& r);
 json::Value to_json(int device, const bgc_soak_result& r);
 json::Value to_json(int device, const bgc_hbm_walk_result& r);
@@ -129,6 +130,8 @@ class Diag {
   json::Value valu(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed);
   // Check of every global and LDS atomic form, refereed by the host, and the atomic rates (see bgc_diag_atomic).
   json::Value atomic(int device, int wgs_per_cu, int rounds, int rate_iters, uint32_t seed);
+  // Per-SIMD march of the whole vector register file and the rotate's move rate (see bgc_diag_regfile).
+  json::Value regfile(int device, int wgs_per_cu, int sweeps, uint32_t seed);
   // MFMA GEMM on the device vs a host fp32 product of the same bf16 operands
   // (deterministic pseudo-random values in [-1, 1]).  Returns max error and the bound.
   json::Value gemm_check(int device, int m, int n, int k, uint32_t seed);
@@ -192,6 +195,7 @@ class Diag {
   BGC_DIAG_ENTRY(cache_, bgc_diag_cache);
   BGC_DIAG_ENTRY(valu_, bgc_diag_valu);
   BGC_DIAG_ENTRY(atomic_, bgc_diag_atomic);
+  BGC_DIAG_ENTRY(regfile_, bgc_diag_regfile);
   BGC_DIAG_ENTRY(burn_, bgc_diag_burn_dtype);
   BGC_DIAG_ENTRY(soak_, bgc_diag_gemm_soak);
   BGC_DIAG_ENTRY(gemm_, bgc_diag_gemm);

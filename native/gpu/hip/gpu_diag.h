@@ -181,6 +181,12 @@ extern "C" {
 //    adder has added to one word is 0 or its trit at any time, a word's partial sums stay within +-8 in any order,
 //    and a word ends at the sum of the trits of its adders if it was visited an odd number of times, else at 0.
 //    A head ends at n = 8 * iters and the group's sums total n (n - 1) / 2.
+//  * Register file (bgc_diag_regfile; regfile_ref.h holds this once).  Registers are numbered r = 0..511: v0..v255,
+//    then a0..a255 as 256..511.  Wave w (global wave index) has the seed ws = mix32(seed + (w + 1) * 0x9e3779b9) and
+//    lane l the hash h = mix32(ws + l).  A fill writes h + r * 0x61c88647 into register r of lane l, pass 1 of the
+//    march the inverse.  Layout 0 leaves out v0..v7 and layout 1 v248..v255.  The rotate fills the ring v8..v255,
+//    a0..a255 (ring index i is register 8 + i, 504 in all) as pass 0 does; a sweep moves the word at index i + 1 to
+//    index i and the one at index 0 to the last, so after s sweeps index i holds the fill of index (i + s) mod 504.
 
 typedef struct {
   uint64_t bytes;          // buffer size tested
@@ -536,6 +542,54 @@ typedef struct {
 // iterations, each wave instruction 256 contiguous bytes, 8 adders per word, the end values checked against their
 // closed forms and the waves' loop times binned by XCC (reported only).  Agent scope and device memory only.
 int bgc_diag_atomic(int device, int wgs_per_cu, int rounds, int rate_iters, uint32_t seed, bgc_atomic_result* out);
+// The register-file check.  Registers are numbered 0..511 (v0..v255, then a0..a255 as 256..511); phases 0..3 are the
+// march's (layout = phase >> 1, pass = phase & 1) and BGC_REGFILE_PHASE_ROTATE is the rotate.
+#define BGC_REGFILE_REGS 512
+#define BGC_REGFILE_TEMPS 8  // registers a march layout (and the rotate) keeps for the check's own use
+#define BGC_REGFILE_PHASE_ROTATE 4
+#define BGC_REGFILE_PHASES 5
+#define BGC_REGFILE_PLANT_SLOTS 8
+// The registers a value plant can name, by slot: the first and last of each half, one in the middle of each, and two
+// of each layout's own eight, which only the other layout verifies.
+#define BGC_REGFILE_PLANT_REGS {0, 5, 128, 250, 255, 256, 384, 511}
+typedef struct {
+  int cus;                     // CUs of the device
+  int cus_seen;                // distinct CUs that ran a march wave
+  int simds;                   // 4 * cus
+  int simds_seen;              // distinct (CU, SIMD) that ran one
+  int regs_marched;            // registers of a lane that some layout marches: 512
+  int ring_regs;               // registers of the rotate's ring: 504
+  uint64_t words_checked;      // waves * 64 * (2 layouts * 2 passes * 504 + ring_regs)
+  uint64_t mismatches;         // vgpr_mismatches + agpr_mismatches + rotate_mismatches
+  uint64_t vgpr_mismatches;    // wrong words of the march in v0..v255
+  uint64_t agpr_mismatches;    // and in a0..a255
+  uint64_t rotate_mismatches;  // wrong words of the ring after the timed rotate
+  int bad_simds;               // (CU, SIMD) with >= 1 wrong word
+  uint32_t bad_bits;           // OR of expected ^ found
+  uint64_t bad_lane_mask;      // bit l: lane l held a wrong word
+  int first_bad_cu_key;        // the lowest (CU key, SIMD) with a wrong word in the march, else in the rotate, and its
+  int first_bad_simd;          // lowest (phase, register, lane); each -1 if none
+  int first_bad_reg;           // 0..511
+  int first_bad_lane;
+  int first_bad_phase;
+  double mov_tops;             // 1e12 lane-moves per second of the timed rotate: waves * 64 * ring_regs * sweeps / rotate_ms
+  int rate_ok;                 // no rotate verify failed
+  double simd_balance;         // fastest / slowest (CU, SIMD) mean loop time of the rotate (1.0 = balanced)
+  int slowest_cu_key;          // the (CU, SIMD) whose rotate waves took longest in the mean; -1 if none ran
+  int slowest_simd;
+  double march_ms, rotate_ms;  // device time of the march launch and of the timed rotate launch
+  double elapsed_ms;           // their sum
+} bgc_regfile_result;
+
+// The vector register file as a memory, 128 KiB per SIMD, which every operand of every other check passes through:
+// cus * `wgs_per_cu` (1..8) workgroups of four waves whose kernel allocates all 512 registers of a lane, so that each
+// wave is alone on a SIMD and its registers are that SIMD's whole file.  The march writes a per-wave pattern into
+// every register of one layout (all but eight), verifies it, writes the inverse and verifies again, then does the same
+// in a second layout that keeps eight other registers: together all 512.  The rotate fills a ring of 504 registers,
+// moves it by one place `sweeps` (1..65536) times between two reads of the constant clock, and verifies where every
+// word arrived: a moving-data check and the move rate.  A wrong word names its CU, SIMD, register, lane and phase.
+// Not covered: the scalar registers, registers under matrix-core traffic, retention over time.
+int bgc_diag_regfile(int device, int wgs_per_cu, int sweeps, uint32_t seed, bgc_regfile_result* out);
 // ---------------------------------------------------------------------------------------------
 // Planted variants: FOR TESTS ONLY.  Each runs the same implementation as the entry point it is
 // named after, with a list of deliberately wrong values ("plants") written into the diagnostic's
@@ -764,6 +818,26 @@ typedef struct {
 int bgc_diag_atomic_delayed(int device, int wgs_per_cu, int rounds, int rate_iters, uint32_t seed, const bgc_atomic_delay_plant* delays,
                             int n, bgc_atomic_result* out);
 
+// Register BGC_REGFILE_PLANT_REGS[slot] of `lane` ^= xor_mask in wave `wave` (global wave index, or every wave with
+// BGC_PLANT_ALL_WAVES) after the fill of `phase` and before its verify; in BGC_REGFILE_PHASE_ROTATE before the sweeps,
+// so the wrong word travels with the ring.  slot below BGC_REGFILE_PLANT_SLOTS, lane 0..63, a non-zero mask, and the
+// phase must hold a pattern in that register (not one of its own eight), else "invalid arguments".
+typedef struct {
+  int wave, phase, slot, lane;
+  uint32_t xor_mask;
+} bgc_regfile_plant;
+int bgc_diag_regfile_planted(int device, int wgs_per_cu, int sweeps, uint32_t seed, const bgc_regfile_plant* plants, int n,
+                             bgc_regfile_result* out);
+// Wave `wave` (or every one) of the timed rotate launch waits `ticks` (1..BGC_DIAG_MAX_DELAY_TICKS) of the constant
+// clock after its loop and before it reads its end time.  No value is touched: the time shows in mov_tops, rotate_ms,
+// slowest_cu_key, slowest_simd and simd_balance only.
+typedef struct {
+  int wave;
+  uint32_t ticks;
+} bgc_regfile_delay_plant;
+int bgc_diag_regfile_delayed(int device, int wgs_per_cu, int sweeps, uint32_t seed, const bgc_regfile_delay_plant* delays, int n,
+                             bgc_regfile_result* out);
+
 // ---------------------------------------------------------------------------------------------
 // Generated data: FOR TESTS ONLY, never loaded by the node agent or the diag worker.  Each runs
 // the same implementation as the entry point it is named after and then copies the data that
@@ -884,6 +958,34 @@ int bgc_diag_atomic_expected(uint32_t seed, int grid, int rounds, const bgc_atom
 // The rate phase's end values for `rate_grid` workgroups: the groups' rows, (group * 64 + row) * 64 + lane, of classes
 // f32, pk bf16 and u32 (rate_grid / 8 * 4 * 4096 words), the groups' heads of rtn (rate_grid / 8 * 4 words).
 int bgc_diag_atomic_rate_expected(uint32_t seed, int rate_grid, int rate_iters, int cls, uint32_t* out, uint64_t capacity_words);
+
+// Where a wave recorded that it ran.
+typedef struct {
+  int cu_key, simd;
+} bgc_regfile_place;
+// bgc_diag_regfile with the plants of bgc_diag_regfile_planted and the delays of bgc_diag_regfile_delayed (either list
+// may be empty); then wave `wave`'s whole file as phase `phase` had it, words[register * 64 + lane]: after the fill and
+// the plants of a march phase, or after the timed rotate's sweeps (the phase's own eight registers are 0); and the place
+// every wave recorded in the march launch and in the timed rotate launch of this very run, march_places[wave] and
+// rotate_places[wave], each with room for `max_waves`.  The copies, 128 KiB and 16 bytes a wave, may not exceed
+// BGC_DIAG_MAX_DATA_BYTES; a launch of more than max_waves waves is refused once the CU count is known.
+int bgc_diag_regfile_data(int device, int wgs_per_cu, int sweeps, uint32_t seed, int wave, int phase, const bgc_regfile_plant* plants, int n,
+                          const bgc_regfile_delay_plant* delays, int n_delay, uint32_t* words, bgc_regfile_place* march_places,
+                          bgc_regfile_place* rotate_places, int max_waves, bgc_regfile_result* out);
+// The layouts (regfile_ref.h).  Touches no device.
+typedef struct {
+  int regs, lanes, temps, ring_regs, plant_slots;
+  uint8_t marched[2][BGC_REGFILE_REGS];             // [layout][register]: 1 if the layout marches it
+  int temp_regs[2][BGC_REGFILE_TEMPS];              // the registers a layout keeps; the rotate keeps layout 0's
+  int ring[BGC_REGFILE_REGS];                       // ring index -> register, ring_regs entries
+  int plant_regs[BGC_REGFILE_PLANT_SLOTS];
+  uint8_t plant_phase_ok[BGC_REGFILE_PLANT_SLOTS][BGC_REGFILE_PHASES];  // 1 if a plant of that slot may name the phase
+} bgc_regfile_layout;
+int bgc_diag_regfile_layout(bgc_regfile_layout* out);
+// What wave `wave` (>= 0) holds when phase `phase` is dumped in a run with `sweeps` sweeps and these plants, as
+// bgc_diag_regfile_data returns it: after `sweeps` sweeps ring index i holds what the fill and the plants put at index
+// (i + sweeps) mod ring_regs, so a planted word is found `sweeps` places down the ring.  Touches no device.
+int bgc_diag_regfile_expected(uint32_t seed, int wave, int phase, int sweeps, const bgc_regfile_plant* plants, int n, uint32_t* words);
 
 // PCI bus id of a HIP device ("0000:05:00.0", lower-case hex) — the key the node agent and
 // the RCCL probe use to match a HIP device (renumbered inside a container) to amdsmi.

@@ -12,6 +12,8 @@
 //    transcendentals, refereed by the host through valu_ref.h) and the vector rates;
 //  * atomic.hip: the check of every global and LDS atomic form in a table per workgroup and in one shared by the
 //    launch, refereed by the host through atomic_ref.h, and the atomic rates;
+//  * regfile.hip: the per-SIMD march of the whole vector register file (v0..v255, a0..a255) in two layouts and the
+//    rotate of 504 registers with its move rate, both held to regfile_ref.h;
 //  * gemm_soak.hip: the ABFT-checked LDS-tiled GEMMs (gemm_soak and the 8-phase gemm_pingpong).
 // The design notes in those files follow the CDNA4 guides (cdna_hip_programming.md,
 // MI355X_MICROARCH.md).

@@ -115,6 +115,13 @@ std::vector<bgc_atomic_plant> atomic_plants(const std::vector<AtomicPlant>& plan
 }
 
 using AccPlant = std::tuple<int, int, int, int, float>;       // check: wave, round, lane, i, delta; rate: wave, lane, chain, i, delta
+using RegfilePlant = std::tuple<int, int, int, int, unsigned>;  // wave or -1, phase, slot, lane, mask
+std::vector<bgc_regfile_plant> regfile_plants(const std::vector<RegfilePlant>& plants) {
+  std::vector<bgc_regfile_plant> p;
+  for (const auto& [wave, phase, slot, lane, mask] : plants) p.push_back({wave, phase, slot, lane, mask});
+  return p;
+}
+
 using LowpPlant = std::tuple<int, int, int, int, int, float>;  // the variant or path (check), the format or path (rate) or the burn's launch in front
 
 // The MX or the classic planted entry on its plant tuples as the C structs.
@@ -270,6 +277,9 @@ void register_gpu(py::module_& m) {
   m.def("diag_atomic", [](int device, int wgs_per_cu, int rounds, int rate_iters, unsigned seed) {
     return dump_nogil([&] { return Diag::instance().atomic(device, wgs_per_cu, rounds, rate_iters, seed); });
   }, py::arg("device"), py::arg("wgs_per_cu") = 2, py::arg("rounds") = 8, py::arg("rate_iters") = 4095, py::arg("seed") = 0x5eed);
+  m.def("diag_regfile", [](int device, int wgs_per_cu, int sweeps, unsigned seed) {
+    return dump_nogil([&] { return Diag::instance().regfile(device, wgs_per_cu, sweeps, seed); });
+  }, py::arg("device"), py::arg("wgs_per_cu") = 2, py::arg("sweeps") = 4096, py::arg("seed") = 0x5eed);
   m.def("diag_gemm", [](int device, int mm, int nn, int kk, const std::string& a, const std::string& b) {
     if (a.size() != static_cast<size_t>(mm) * kk * 2 || b.size() != static_cast<size_t>(kk) * nn * 2) {
       throw std::invalid_argument("A must be M*K and B K*N bf16 values");
@@ -632,6 +642,50 @@ void register_gpu(py::module_& m) {
                                                                                           reinterpret_cast<uint32_t*>(data.data()), data.size() / 4));
     return py::bytes(data);
   }, py::arg("seed"), py::arg("rate_grid"), py::arg("rate_iters"), py::arg("cls"));
+  // register-file plants (wave or -1, phase, slot, lane, mask) and delays (wave or -1, ticks of the constant clock)
+  m.def("diag_regfile_planted", [](int device, int wgs_per_cu, int sweeps, unsigned seed, const std::vector<RegfilePlant>& plants) {
+    const std::vector<bgc_regfile_plant> p = regfile_plants(plants);
+    return planted("regfile diag", BGC_DIAG_ENTRY(bgc_diag_regfile_planted), device, wgs_per_cu, sweeps, seed, p.data(), count(p));
+  }, py::arg("device"), py::arg("wgs_per_cu"), py::arg("sweeps"), py::arg("seed"), py::arg("plants"));
+  m.def("diag_regfile_delayed", [](int device, int wgs_per_cu, int sweeps, unsigned seed, const std::vector<std::tuple<int, unsigned>>& delays) {
+    std::vector<bgc_regfile_delay_plant> d;
+    for (const auto& [wave, ticks] : delays) d.push_back({wave, ticks});
+    return planted("regfile diag", BGC_DIAG_ENTRY(bgc_diag_regfile_delayed), device, wgs_per_cu, sweeps, seed, d.data(), count(d));
+  }, py::arg("device"), py::arg("wgs_per_cu"), py::arg("sweeps"), py::arg("seed"), py::arg("delays"));
+  // the result, the wave's 512 x 64 words, and every wave's (CU key, SIMD) of the march and of the timed rotate launch
+  // (room for a device of 512 CUs), as bytes
+  m.def("diag_regfile_data", [](int device, int wgs_per_cu, int sweeps, unsigned seed, int wave, int phase, const std::vector<RegfilePlant>& plants,
+                                const std::vector<std::tuple<int, unsigned>>& delays) {
+    const std::vector<bgc_regfile_plant> p = regfile_plants(plants);
+    std::vector<bgc_regfile_delay_plant> d;
+    for (const auto& [w, ticks] : delays) d.push_back({w, ticks});
+    const int max_waves = 512 * 8 * 4;
+    std::string words(BGC_REGFILE_REGS * 64 * 4, '\0'), march(max_waves * sizeof(bgc_regfile_place), '\0'), rotate(march.size(), '\0');
+    Value v;
+    {
+      py::gil_scoped_release nogil;
+      v = Diag::instance().call("regfile diag", BGC_DIAG_ENTRY(bgc_diag_regfile_data), device, wgs_per_cu, sweeps, seed, wave, phase, p.data(), count(p),
+                                d.data(), count(d), reinterpret_cast<uint32_t*>(words.data()), reinterpret_cast<bgc_regfile_place*>(march.data()),
+                                reinterpret_cast<bgc_regfile_place*>(rotate.data()), max_waves);
+    }
+    const size_t waves = static_cast<size_t>(v.get("cus").as_int()) * wgs_per_cu * 4;
+    march.resize(waves * sizeof(bgc_regfile_place));
+    rotate.resize(waves * sizeof(bgc_regfile_place));
+    return py::make_tuple(v.dump(), py::bytes(words), py::bytes(march), py::bytes(rotate));
+  }, py::arg("device"), py::arg("wgs_per_cu"), py::arg("sweeps"), py::arg("seed"), py::arg("wave"), py::arg("phase"), py::arg("plants"),
+     py::arg("delays"));
+  m.def("diag_regfile_layout", [] {
+    std::string layout(sizeof(bgc_regfile_layout), '\0');
+    Diag::instance().check("regfile diag", BGC_DIAG_ENTRY(bgc_diag_regfile_layout)(reinterpret_cast<bgc_regfile_layout*>(layout.data())));
+    return py::bytes(layout);
+  });
+  m.def("diag_regfile_expected", [](unsigned seed, int wave, int phase, int sweeps, const std::vector<RegfilePlant>& plants) {
+    const std::vector<bgc_regfile_plant> p = regfile_plants(plants);
+    std::string words(BGC_REGFILE_REGS * 64 * 4, '\0');
+    Diag::instance().check("regfile diag", BGC_DIAG_ENTRY(bgc_diag_regfile_expected)(seed, wave, phase, sweeps, p.data(), count(p),
+                                                                                     reinterpret_cast<uint32_t*>(words.data())));
+    return py::bytes(words);
+  }, py::arg("seed"), py::arg("wave"), py::arg("phase"), py::arg("sweeps"), py::arg("plants"));
   m.def("diag_valu_trans_ulps", [] {
     return py::make_tuple(BGC_VALU_EXP_ULPS, BGC_VALU_LOG_ULPS, BGC_VALU_RCP_ULPS, BGC_VALU_RSQ_ULPS, BGC_VALU_SQRT_ULPS);
   });
