@@ -45,7 +45,7 @@ RUN cmake -S . -B build -G Ninja -DCMAKE_BUILD_TYPE=Release -DBGC_PYTHON=OFF && 
     ninja -C build node-agent && \
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared \
       -mllvm -amdgpu-mfma-vgpr-form=1 -Inative/gpu/hip native/gpu/hip/gpu_diag.hip native/gpu/hip/hbm.hip \
-      native/gpu/hip/mfma.hip native/gpu/hip/lds.hip native/gpu/hip/cache.hip native/gpu/hip/valu.hip native/gpu/hip/atomic.hip native/gpu/hip/regfile.hip native/gpu/hip/gemm_soak.hip \
+      native/gpu/hip/mfma.hip native/gpu/hip/lds.hip native/gpu/hip/cache.hip native/gpu/hip/valu.hip native/gpu/hip/atomic.hip native/gpu/hip/regfile.hip native/gpu/hip/xlane.hip native/gpu/hip/gemm_soak.hip \
       -o bin/libbgc_gpu_diag.so
 # The agent dlopen()s libamd_smi and the diagnostics library (which links the HIP
 # runtime): collect exactly those plus, to a fixpoint, their ROCm dependencies.  The same

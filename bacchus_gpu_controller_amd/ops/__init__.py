@@ -1,4 +1,4 @@
-"""HIP/CDNA4 GPU health kernels (native/gpu/hip/: hbm.hip, mfma.hip, lds.hip, cache.hip, valu.hip, atomic.hip, regfile.hip, gemm_soak.hip) exposed to Python.
+"""HIP/CDNA4 GPU health kernels (native/gpu/hip/: hbm.hip, mfma.hip, lds.hip, cache.hip, valu.hip, atomic.hip, regfile.hip, xlane.hip, gemm_soak.hip) exposed to Python.
 
 These are the only compute kernels in the framework: the reference controller has none
 (SURVEY §2.5).  They back the node agent's diagnostics before a GPU is advertised
@@ -22,6 +22,8 @@ These are the only compute kernels in the framework: the reference controller ha
   returning adds as tickets) in a table per workgroup and in one shared by the launch, refereed by the host CPU; then the atomic rates
 * ``regfile(device)``   — a march of every SIMD's whole vector register file (512 registers a lane, 128 KiB a SIMD) in two
   layouts, attributed to CU, SIMD, register and lane; then a rotate of 504 registers, a moving-data check and the move rate
+* ``xlane(device)``     — the cross-lane paths (DPP, the half-wave swaps, the LDS crossbar's permutes, the moves between lanes
+  and scalar registers) on every SIMD, refereed by the host CPU and attributed to CU, SIMD and lane; then the cross-lane rates
 * ``gemm_check(device)``— a bf16 GEMM on the matrix cores checked element by element against
   a double-precision product of the same operands on the host
 * ``gemm_soak(device)`` — the sustained-throughput soak: the 8-phase ping-pong GEMM
@@ -36,11 +38,11 @@ These are the only compute kernels in the framework: the reference controller ha
 * ``pcie(device)``      — host<->device copy bandwidth, pinned
 * ``device_bdf(device)``— the HIP device's PCI address, to match it to amdsmi / kubelet
 * ``hbm_planted``, ``hbm_walk_planted``, ``pcie_planted``, ``mfma_planted``,
-  ``mfma_lowp_planted``, ``mfma_classic_planted``, ``lds_planted``, ``cache_planted``, ``valu_planted``, ``atomic_planted``, ``regfile_planted``, ``gemm_soak_planted``, ``burn_planted`` — for tests: the same diagnostics with wrong
+  ``mfma_lowp_planted``, ``mfma_classic_planted``, ``lds_planted``, ``cache_planted``, ``valu_planted``, ``atomic_planted``, ``regfile_planted``, ``xlane_planted``, ``gemm_soak_planted``, ``burn_planted`` — for tests: the same diagnostics with wrong
   values planted in their own data, to show that they are detected (see below)
-* ``mfma_delayed``, ``burn_delayed``, ``cache_delayed``, ``valu_delayed``, ``atomic_delayed``, ``regfile_delayed`` — for tests: the matrix-core throughput, the burn, the L2 rate, the vector and the atomic rates with
+* ``mfma_delayed``, ``burn_delayed``, ``cache_delayed``, ``valu_delayed``, ``atomic_delayed``, ``regfile_delayed``, ``xlane_delayed`` — for tests: the matrix-core throughput, the burn, the L2 rate, the vector and the atomic rates with
   chosen waves, launches or workgroups made slow by a known time, to show that it reaches the rates
-* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile``, ``mfma_classic_tile``, ``lds_data``, ``cache_data``, ``valu_data``, ``valu_expected``, ``atomic_data``, ``atomic_expected``, ``atomic_rate_expected``, ``regfile_data``, ``regfile_expected``, ``regfile_layout`` — for tests:
+* ``hbm_data``, ``hbm_walk_data``, ``pcie_data``, ``gemm_soak_data``, ``mfma_tile``, ``mfma_classic_tile``, ``lds_data``, ``cache_data``, ``valu_data``, ``valu_expected``, ``atomic_data``, ``atomic_expected``, ``atomic_rate_expected``, ``regfile_data``, ``regfile_expected``, ``regfile_layout``, ``xlane_data``, ``xlane_expected`` — for tests:
   the same diagnostics, returning the data they generated for themselves (see below)
 
 All fail loudly (RuntimeError) if ``libbgc_gpu_diag.so`` or the GPU is missing; there
@@ -216,6 +218,31 @@ def regfile(device=0, wgs_per_cu=REGFILE_WGS_PER_CU, sweeps=REGFILE_SWEEPS, seed
     return json.loads(native().diag_regfile(device, wgs_per_cu, sweeps, seed))
 
 
+XLANE_CLASSES = ("row", "wave", "mask", "alu", "swap", "lds", "lane", "exec")  # BGC_XLANE_*: the order of class_mismatches
+XLANE_CLASS_WORDS = (12, 6, 6, 3, 4, 6, 6, 4)  # 32-bit result words of a class per round, 47 in all (BGC_XLANE_ROUND_WORDS)
+XLANE_ROUND_WORDS = 47
+XLANE_RATE_CLASSES = ("dpp", "swap", "bpermute", "swizzle")  # BGC_XLANE_RATE_*: the order of rate_ms
+# Defaults of xlane(), from tools/probes/xlane_rate_probe.py on the MI355X (profiles/xlane_diag/rates.json, 12 runs per point, each
+# right after an MFMA check).  Every SIMD is checked by two waves.  The rates rise with the iterations until the launch outlasts its
+# ramp: at 2 waves per SIMD the DPP move reads 27.9-29.0 x 10^12 lane-moves per second at 1024 iterations, 31.7-32.3 at 4096 and
+# 32.8-33.7 at 16384, where the run is 4.7 ms of kernels (2.7 ms of them the ds_bpermute launch) and 6.2 ms with its copies and the
+# host referee.  8 waves per SIMD read more (35.4-36.3) at 4 times the time.
+XLANE_WAVES_PER_SIMD = 2
+XLANE_ROUNDS = 16
+XLANE_RATE_ITERS = 16384
+
+
+def xlane(device=0, waves_per_simd=XLANE_WAVES_PER_SIMD, rounds=XLANE_ROUNDS, rate_iters=XLANE_RATE_ITERS, seed=0x5EED):
+    """The cross-lane paths: cus * `waves_per_simd` (1..8) workgroups of four waves each run `rounds` (1..64) rounds of a
+    fixed sequence of DPP moves and arithmetic, half-wave swaps, ds_bpermute / ds_permute / ds_swizzle, v_readlane,
+    v_readfirstlane, v_writelane, ballots and moves under a partial EXEC mask in eight classes (XLANE_CLASSES) on hashed
+    operands and write a digest per lane and class; the host CPU recomputes every digest and names the CU, SIMD and
+    destination lane of a wrong value.  Then each rate class (XLANE_RATE_CLASSES) runs `rate_iters` (1..65536) steps of
+    8 chains per lane: ``dpp_tops``, ``swap_tops``, ``bpermute_tops``, ``swizzle_tops`` (10^12 lane-moves per second);
+    ``rate_ms`` in that order."""
+    return json.loads(native().diag_xlane(device, waves_per_simd, rounds, rate_iters, seed))
+
+
 def gemm_check(device=0, m=4096, n=4096, k=4096, seed=0x5EED):
     return json.loads(native().diag_gemm_check(device, m, n, k, seed))
 
@@ -316,6 +343,16 @@ def valu_planted(check_plants, rate_plants=(), device=0, waves_per_simd=1, round
     return json.loads(native().diag_valu_planted(device, waves_per_simd, rounds, rate_iters, seed, check, rate))
 
 
+def xlane_planted(check_plants, rate_plants=(), device=0, waves_per_simd=1, rounds=2, rate_iters=16, seed=0x5EED):
+    """xlane() with check plants (wave or -1 for every wave, class, round, destination lane, result word of the class, xor
+    mask), applied to the word before it is folded into the digest, and rate plants (wave or -1, rate class, lane, chain
+    0..7, xor mask), applied to the chain's end value after the loop of that class's timed launch.  Classes by name
+    (XLANE_CLASSES, XLANE_RATE_CLASSES) or number."""
+    check = [(p[0], _valu_code(XLANE_CLASSES, p[1])) + tuple(p[2:]) for p in check_plants]
+    rate = [(p[0], _valu_code(XLANE_RATE_CLASSES, p[1])) + tuple(p[2:]) for p in rate_plants]
+    return json.loads(native().diag_xlane_planted(device, waves_per_simd, rounds, rate_iters, seed, check, rate))
+
+
 def _atomic_plants(plants):
     """(placement, class, word, wave, round, lane, times, mask) with the placement and the class by name or number"""
     return [(_valu_code(ATOMIC_PLACEMENTS, p[0]), _valu_code(ATOMIC_CLASSES, p[1])) + tuple(p[2:]) for p in plants]
@@ -354,6 +391,14 @@ def regfile_delayed(delays, device=0, wgs_per_cu=1, sweeps=64, seed=0x5EED):
     clock after its loop and before it reads its end time.  No value is touched; the time shows in mov_tops, rotate_ms,
     slowest_cu_key, slowest_simd and simd_balance."""
     return json.loads(native().diag_regfile_delayed(device, wgs_per_cu, sweeps, seed, [tuple(d) for d in delays]))
+
+
+def xlane_delayed(delays, device=0, waves_per_simd=1, rounds=2, rate_iters=16, seed=0x5EED):
+    """xlane() with (wave or -1, rate class, ticks): that wave of that class's timed launch waits `ticks` of the 100 MHz
+    constant clock after its loop and before it reads its end time.  No value is touched; the time shows in the class's
+    rate, rate_ms, slowest_cu_key and cu_balance."""
+    return json.loads(native().diag_xlane_delayed(device, waves_per_simd, rounds, rate_iters, seed,
+                                                  [(d[0], _valu_code(XLANE_RATE_CLASSES, d[1]), d[2]) for d in delays]))
 
 
 def valu_delayed(delays, device=0, waves_per_simd=1, rounds=2, rate_iters=16, seed=0x5EED):
@@ -490,6 +535,32 @@ def valu_expected(rounds, seed=0x5EED):
     """What the host referee expects of every wave, shaped as valu_data's wave (``cu_key``, ``simd`` and ``rate_cu_key`` -1; the
     trans words are double-precision libm rounded to fp32, which no digest is compared with).  Needs no GPU."""
     return _valu_wave(native().diag_valu_expected(seed, rounds), rounds)
+
+
+XLANE_WAVE = np.dtype([("cu_key", "<i4"), ("simd", "<i4"), ("rate_cu_key", "<i4", 4), ("digests", "<u4", (8, 64)), ("raw", "<u4", (64, XLANE_ROUND_WORDS, 64))])
+
+
+def _xlane_wave(data, rounds):
+    w = np.frombuffer(data, dtype=XLANE_WAVE)[0]
+    return {"cu_key": int(w["cu_key"]), "simd": int(w["simd"]), "rate_cu_key": [int(k) for k in w["rate_cu_key"]], "digests": w["digests"], "raw": w["raw"][:rounds]}
+
+
+def xlane_data(wave, check_plants=(), rate_plants=(), delays=(), device=0, waves_per_simd=1, rounds=2, rate_iters=16, seed=0x5EED):
+    """(result, check wave `wave` of that run) with the plants of xlane_planted and the delays of xlane_delayed applied.
+    The wave: ``cu_key`` and ``simd`` where it ran in the check launch, ``rate_cu_key`` the CU it ran on in each rate
+    class's timed launch, ``digests`` [class, lane] as it wrote them, ``raw`` [round, result word of the round, lane] as
+    it folded them, all uint32."""
+    check = [(p[0], _valu_code(XLANE_CLASSES, p[1])) + tuple(p[2:]) for p in check_plants]
+    rate = [(p[0], _valu_code(XLANE_RATE_CLASSES, p[1])) + tuple(p[2:]) for p in rate_plants]
+    slow = [(d[0], _valu_code(XLANE_RATE_CLASSES, d[1]), d[2]) for d in delays]
+    r, data = native().diag_xlane_data(device, waves_per_simd, rounds, rate_iters, seed, wave, check, rate, slow)
+    return json.loads(r), _xlane_wave(data, rounds)
+
+
+def xlane_expected(rounds, seed=0x5EED):
+    """What the host referee expects of every wave, shaped as xlane_data's wave (``cu_key``, ``simd`` and ``rate_cu_key``
+    -1).  Needs no GPU."""
+    return _xlane_wave(native().diag_xlane_expected(seed, rounds), rounds)
 
 
 ATOMIC_LAYOUT = np.dtype([("grid", "<i4"), ("rate_grid", "<i4"), ("rounds", "<i4"), ("waves", "<i4"), ("pairs", "<u4"), ("rows", "<u4", (2, 8)),

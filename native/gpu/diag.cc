@@ -389,6 +389,45 @@ json::Value to_json(int device, const bgc_regfile_result& r) {
                               {"passed", clean && r.rate_ok != 0 && r.simds_seen == r.simds}});
 }
 
+json::Value to_json(int device, const bgc_xlane_result& r) {
+  static const char* const kClasses[BGC_XLANE_CLASSES] = {"row", "wave", "mask", "alu", "swap", "lds", "lane", "exec"};
+  json::Value by_class = json::Value::array(), rate_ms = json::Value::array();
+  uint64_t mism = 0;
+  for (int c = 0; c < BGC_XLANE_CLASSES; ++c) {
+    by_class.push_back(static_cast<unsigned long long>(r.mismatches[c]));
+    mism += r.mismatches[c];
+  }
+  for (int c = 0; c < BGC_XLANE_RATE_CLASSES; ++c) rate_ms.push_back(r.rate_ms[c]);
+  char lanes[24];
+  std::snprintf(lanes, sizeof(lanes), "0x%016llx", static_cast<unsigned long long>(r.bad_lanes));
+  const bool clean = mism == 0;
+  return json::Value::object({{"device", device},
+                              {"cus", r.cus},
+                              {"cus_seen", r.cus_seen},
+                              {"simds_seen", r.simds_seen},
+                              {"values_checked", static_cast<unsigned long long>(r.values_checked)},
+                              {"class_mismatches", by_class},  // row, wave, mask, alu, swap, lds, lane, exec
+                              {"mismatches", static_cast<unsigned long long>(mism)},
+                              {"bad_cus", r.bad_cus},
+                              {"bad_simds", r.bad_simds},
+                              {"bad_cu_keys", bad_cu_keys(r)},
+                              {"first_bad_cu_key", clean ? json::Value() : json::Value(r.first_bad_cu_key)},
+                              {"first_bad_simd", clean ? json::Value() : json::Value(r.first_bad_simd)},
+                              {"first_bad_lane", clean ? json::Value() : json::Value(r.first_bad_lane)},
+                              {"first_bad_class", clean ? json::Value() : json::Value(std::string(kClasses[r.first_bad_class]))},
+                              {"bad_lanes", clean ? json::Value() : json::Value(std::string(lanes))},
+                              {"dpp_tops", r.rate[BGC_XLANE_RATE_DPP]},  // all four in 1e12 lane-moves per second
+                              {"swap_tops", r.rate[BGC_XLANE_RATE_SWAP]},
+                              {"bpermute_tops", r.rate[BGC_XLANE_RATE_BPERMUTE]},
+                              {"swizzle_tops", r.rate[BGC_XLANE_RATE_SWIZZLE]},
+                              {"rate_ms", rate_ms},  // dpp, swap, bpermute, swizzle
+                              {"rate_ok", r.rate_ok != 0},
+                              {"slowest_cu_key", r.slowest_cu_key},
+                              {"cu_balance", r.cu_balance},
+                              {"elapsed_ms", r.elapsed_ms},
+                              {"passed", clean && r.rate_ok != 0}});
+}
+
 json::Value to_json(int device, const bgc_pcie_result& r) {
   return json::Value::object({{"device", device}, {"bytes", static_cast<unsigned long long>(r.bytes)},
                               {"iters", r.iters}, {"h2d_gbps", r.h2d_gbps}, {"d2h_gbps", r.d2h_gbps},
@@ -464,6 +503,10 @@ json::Value Diag::atomic(int device, int wgs_per_cu, int rounds, int rate_iters,
 
 json::Value Diag::regfile(int device, int wgs_per_cu, int sweeps, uint32_t seed) {
   return call("regfile diag", regfile_, device, wgs_per_cu, sweeps, seed);
+}
+
+json::Value Diag::xlane(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed) {
+  return call("xlane diag", xlane_, device, waves_per_simd, rounds, rate_iters, seed);
 }
 
 json::Value Diag::pcie(int device, uint64_t bytes, int iters, uint32_t seed) {

@@ -103,6 +103,7 @@ json::Value to_json(int device, const bgc_cache_result& r);
 json::Value to_json(int device, const bgc_valu_result& r);
 json::Value to_json(int device, const bgc_atomic_result& r);
 json::Value to_json(int device, const bgc_regfile_result& r);
+json::Value to_json(int device, const bgc_xlane_result& r);
 json::Value to_json(int device, const bgc_pcie_result& r);
 json::Value to_json(int device, const bgc_soak_result& r);
 json::Value to_json(int device, const bgc_hbm_walk_result& r);
@@ -132,6 +133,9 @@ class Diag {
   json::Value atomic(int device, int wgs_per_cu, int rounds, int rate_iters, uint32_t seed);
   // Per-SIMD march of the whole vector register file and the rotate's move rate (see bgc_diag_regfile).
   json::Value regfile(int device, int wgs_per_cu, int sweeps, uint32_t seed);
+  // Per-SIMD check of the cross-lane paths (DPP, half-wave swaps, LDS crossbar, lane <-> scalar), refereed by the host,
+  // and the cross-lane rates (see bgc_diag_xlane).
+  json::Value xlane(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed);
   // MFMA GEMM on the device vs a host fp32 product of the same bf16 operands
   // (deterministic pseudo-random values in [-1, 1]).  Returns max error and the bound.
   json::Value gemm_check(int device, int m, int n, int k, uint32_t seed);
@@ -196,6 +200,7 @@ class Diag {
   BGC_DIAG_ENTRY(valu_, bgc_diag_valu);
   BGC_DIAG_ENTRY(atomic_, bgc_diag_atomic);
   BGC_DIAG_ENTRY(regfile_, bgc_diag_regfile);
+  BGC_DIAG_ENTRY(xlane_, bgc_diag_xlane);
   BGC_DIAG_ENTRY(burn_, bgc_diag_burn_dtype);
   BGC_DIAG_ENTRY(soak_, bgc_diag_gemm_soak);
   BGC_DIAG_ENTRY(gemm_, bgc_diag_gemm);

@@ -1,4 +1,4 @@
-// Shared by the diagnostics' sources (gpu_diag.hip, hbm.hip, mfma.hip, lds.hip, cache.hip, valu.hip, atomic.hip, regfile.hip, gemm_soak.hip): vector
+// Shared by the diagnostics' sources (gpu_diag.hip, hbm.hip, mfma.hip, lds.hip, cache.hip, valu.hip, atomic.hip, regfile.hip, xlane.hip, gemm_soak.hip): vector
 // types, the hash, the CU a wave runs on, the marches' pattern and wrong-word record, the delay plants' wait, a rate
 // launch's timing bin, the last-error string and the host helpers every entry point uses: device buffers and events,
 // the test plants' list, upload and beyond-the-launch refusal, the constant clock's rate, the rate formula and

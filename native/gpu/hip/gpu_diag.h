@@ -187,6 +187,61 @@ extern "C" {
 //    march the inverse.  Layout 0 leaves out v0..v7 and layout 1 v248..v255.  The rotate fills the ring v8..v255,
 //    a0..a255 (ring index i is register 8 + i, 504 in all) as pass 0 does; a sweep moves the word at index i + 1 to
 //    index i and the one at index 0 to the last, so after s sweeps index i holds the fill of index (i + s) mod 504.
+//  * Cross-lane (bgc_diag_xlane; xlane_ref.h holds this once).  Every wave computes the same values.  Operand word k
+//    of (class cls, round r, lane l) is the vector ALU's hash, w_k = mix32(seed ^ mix32(cls << 24 | r << 16 | k << 8 |
+//    l)); a wave-uniform word is the hash of lane 64, which no wave has: u_k = w(cls, r, k, 64).  The model of the
+//    instructions, written from the ISA manual and held to the MI355X by the GPU tests:
+//      DPP gate.  Lane l is in row l / 16 and bank (l mod 16) / 4.  If its row_mask bit or its bank_mask bit is 0, or
+//        EXEC disables it, the lane keeps `old` (the destination register's content).  Otherwise it takes the source
+//        lane s; if s is invalid or disabled by EXEC it takes 0 with bound_ctrl:1 and keeps `old` with bound_ctrl:0.
+//      DPP source lanes.  quad_perm: (l & ~3) + sel[l & 3].  row_shr:n: l - n, row_shl:n: l + n, both invalid outside
+//        the row.  row_ror:n: the row's base + ((l mod 16) - n) mod 16.  wave_shr:1: l - 1, lane 0 invalid; wave_ror:1:
+//        (l - 1) mod 64; wave_shl:1: l + 1, lane 63 invalid; wave_rol:1: (l + 1) mod 64.  row_mirror: base + 15 - l mod
+//        16.  row_half_mirror: (l & ~7) + 7 - (l & 7).  row_bcast:15: lane 15 of the previous row; a lane of row 0
+//        reads itself.  row_bcast:31: lane 31 for rows 2 and 3; a lane of rows 0 and 1 reads itself.  (Measured on the
+//        MI355X with bound_ctrl:0: those rows are not invalid, they receive their own source and not `old`.)
+//      A VOP2 with a DPP operand, v_add_u32_dpp vdst, src0, src1: vdst = dpp(src0) + src1 under the same gate, a lane
+//        that is not written keeping vdst.
+//      v_permlane32_swap vdst, src: lanes 32..63 of vdst swap with lanes 0..31 of src.  v_permlane16_swap: rows 1 and
+//        3 of vdst swap with rows 0 and 2 of src.
+//      ds_bpermute: dst[l] = src[(addr[l] >> 2) & 63]; an inactive source lane gives 0, an inactive lane is not
+//        written.  ds_permute: dst[(addr[l] >> 2) & 63] = src[l].
+//      ds_swizzle, bit mode: within each 32-lane half s = ((l & and) | or) ^ xor, the fields being offset bits 4:0,
+//        9:5 and 14:10.  Quad mode (bit 15 set): offset bits 7:0 act as a quad_perm.
+//      v_readfirstlane: the lowest lane set in EXEC.  v_mbcnt_lo then _hi: the number of set mask bits below the lane.
+//    A round of a class produces these 32-bit result words, in this order (47 in all; BGC_XLANE_ROUND_WORDS).  Unless
+//    said otherwise the source is w_0, `old` is w_1, both masks are 0xf and bound_ctrl is 0.
+//      row (12), v_mov_b32_dpp:  quad_perm:[3,2,1,0];  [1,0,3,2];  [2,2,0,0];  row_shl:1;  row_shl:7;  row_shr:1;
+//        row_shr:12;  row_ror:1;  row_ror:8;  row_ror:15;  row_mirror;  row_half_mirror.
+//      wave (6), alike:  wave_shl:1;  wave_rol:1;  wave_shr:1;  wave_ror:1;  row_bcast:15;  row_bcast:31.
+//      mask (6), alike:  row_shr:1 bound_ctrl:1;  wave_shl:1 bound_ctrl:1;  row_ror:3 row_mask:0xa;  row_ror:3
+//        bank_mask:0x5;  row_bcast:15 row_mask:0xa;  row_shr:3 row_mask:0x6 bank_mask:0x9 bound_ctrl:1.
+//      alu (3), all modulo 2^32:  v_add_u32_dpp row_shr:1 bound_ctrl:1 of w_0 and w_1 into a register that holds w_2;
+//        v_min_u32_dpp row_ror:8 alike;  the inclusive prefix sum of w_2 over the 64 lanes by the DPP scan: acc =
+//        dpp(x) + x with row_shr:1, acc += dpp(x) with row_shr:2 and row_shr:3 (all three bound_ctrl:1), then acc +=
+//        dpp(acc) with row_shr:4 bank_mask:0xe, row_shr:8 bank_mask:0xc, row_bcast:15 row_mask:0xa and row_bcast:31
+//        row_mask:0xc.
+//      swap (4), vdst = w_0, src = w_1:  vdst, then src after v_permlane16_swap_b32;  the same after
+//        v_permlane32_swap_b32 of the original two.
+//      lds (6):  ds_bpermute_b32 with address (w_1 & 63) << 2;  ds_bpermute_b32 with address ((l + 1 + u_0 mod 63) &
+//        63) << 2, a rotation by 1..63;  ds_permute_b32 with address (((u_1 | 1) l + u_2) & 63) << 2, a bijection;
+//        ds_swizzle_b32 with and 0x1b, or 0x04, xor 0x11;  with and 0x0f, or 0x10, xor 0x0a;  in quad mode with
+//        [1,3,0,2].
+//      lane (6):  v_readlane_b32 of lane u_0 & 63 of w_0, in every lane;  v_readfirstlane_b32 of w_1, alike;  w_2 with
+//        u_1 in lane u_2 & 63 by v_writelane_b32;  the low word of the ballot of w_0 & 1, in every lane;  its high
+//        word;  v_mbcnt_lo then v_mbcnt_hi of that ballot.
+//      exec (4), under the EXEC mask M = ((u_1 << 32 | u_0) | 1 << on) & ~(1 << off) with on = u_2 & 63 and off = (on +
+//        1 + u_3 mod 63) & 63:  v_mov_b32_dpp wave_ror:1;  the same with bound_ctrl:1;  ds_bpermute_b32 with address
+//        (w_2 & 63) << 2.  A lane that M disables holds `old`, w_1, in these three.  Then v_readfirstlane_b32 under M,
+//        a scalar that every lane folds once EXEC is restored.
+//    Digest: d(cls, l) starts at 0x9e3779b9 + cls and folds every result word v as d = mix32(d ^ v), as the vector
+//    ALU's.  All eight classes are exact: the host compares every digest with its own, and there is no consensus.
+//    Rate phase: 8 chains per lane, chain c of lane l filled with mix32(seed ^ (0x10000 | c << 8 | l)).  Every step is a
+//    permutation of the wave's 8 * 64 values: dpp moves every chain by v_mov_b32_dpp row_ror:1;  swap exchanges
+//    chains 2 j and 2 j + 1 by v_permlane32_swap_b32;  bpermute reads lane (l + 1) mod 64 by ds_bpermute_b32;
+//    swizzle reads lane l ^ 0x15 of its half by ds_swizzle_b32 (and 0x1f, or 0, xor 0x15).  After `rate_iters` steps a
+//    chain holds the fill moved by that permutation's rate_iters-th power.  The end digest of a lane starts at
+//    0x85ebca6b + rate class and folds chain 0's word, then chain 1's, ...
 
 typedef struct {
   uint64_t bytes;          // buffer size tested
@@ -590,6 +645,56 @@ typedef struct {
 // word arrived: a moving-data check and the move rate.  A wrong word names its CU, SIMD, register, lane and phase.
 // Not covered: the scalar registers, registers under matrix-core traffic, retention over time.
 int bgc_diag_regfile(int device, int wgs_per_cu, int sweeps, uint32_t seed, bgc_regfile_result* out);
+// The cross-lane check's instruction classes, in the order of every [8] below and of a plant's `cls`.
+#define BGC_XLANE_ROW 0   // v_mov_b32_dpp: quad_perm, row_shl, row_shr, row_ror, row_mirror, row_half_mirror
+#define BGC_XLANE_WAVE 1  // v_mov_b32_dpp: wave_shl, wave_rol, wave_shr, wave_ror, row_bcast:15, row_bcast:31
+#define BGC_XLANE_MASK 2  // v_mov_b32_dpp with row_mask, bank_mask and bound_ctrl
+#define BGC_XLANE_ALU 3   // v_add_u32_dpp, v_min_u32_dpp, the DPP prefix scan
+#define BGC_XLANE_SWAP 4  // v_permlane16_swap_b32, v_permlane32_swap_b32
+#define BGC_XLANE_LDS 5   // ds_bpermute_b32, ds_permute_b32, ds_swizzle_b32: the LDS crossbar, no LDS memory
+#define BGC_XLANE_LANE 6  // v_readlane_b32, v_readfirstlane_b32, v_writelane_b32, the ballot (v_cmp), v_mbcnt_lo / _hi
+#define BGC_XLANE_EXEC 7  // v_mov_b32_dpp, ds_bpermute_b32 and v_readfirstlane_b32 under a partial EXEC mask
+#define BGC_XLANE_CLASSES 8
+#define BGC_XLANE_ROUND_WORDS 47  // 32-bit result words of a lane per round: 12 + 6 + 6 + 3 + 4 + 6 + 6 + 4
+// The rate phase's classes, in the order of every [4] below; all in 1e12 lane-moves per second (a 32-bit value
+// arriving in a lane; a swap writes two registers and counts 128 a wave).
+#define BGC_XLANE_RATE_DPP 0       // v_mov_b32_dpp row_ror:1
+#define BGC_XLANE_RATE_SWAP 1      // v_permlane32_swap_b32
+#define BGC_XLANE_RATE_BPERMUTE 2  // ds_bpermute_b32
+#define BGC_XLANE_RATE_SWIZZLE 3   // ds_swizzle_b32
+#define BGC_XLANE_RATE_CLASSES 4
+typedef struct {
+  int cus;                     // CUs of the device
+  int cus_seen;                // distinct CUs that ran a check wave
+  int simds_seen;              // distinct (CU, SIMD) that ran one
+  uint64_t values_checked;     // result words folded into digests: waves * 64 * rounds * BGC_XLANE_ROUND_WORDS
+  uint64_t mismatches[8];      // (wave, lane) digests that differ from the host's, by class
+  int bad_cus;                 // CUs with >= 1 mismatch
+  int bad_simds;               // (CU, SIMD) with >= 1 mismatch
+  int first_bad_cu_key;        // the mismatch with the lowest (CU key, SIMD, wave, class, lane); each -1 if none
+  int first_bad_simd;          // 0..3
+  int first_bad_lane;          // the destination lane
+  int first_bad_class;
+  uint64_t bad_lanes;          // bit l: destination lane l mismatched in some wave
+  double rate[4];              // each rate class's launch, 1e12 lane-moves per second
+  double rate_ms[4];           // device time of that launch
+  int rate_ok;                 // every lane's end digest of every rate launch matched
+  int slowest_cu_key;          // CU whose rate waves took longest in the mean over the four launches, -1 if none ran
+  double cu_balance;           // fastest / slowest CU mean wave time (1.0 = balanced)
+  double elapsed_ms;           // the check launch and the four timed launches
+  int bad_cu_keys[64];
+} bgc_xlane_result;
+
+// The paths that move a value from one lane of a wave to another, which carry every wave reduction (softmax and
+// layer-norm row sums, __shfl_*, ballots, readfirstlane broadcasts, the matrix-core epilogue transposes): the DPP
+// network of each SIMD's vector ALU, the swap path between half-waves, the LDS crossbar and the path between vector
+// lanes and scalar registers.  cus * `waves_per_simd` (1..8) workgroups of four waves, normally one per SIMD of a CU,
+// each run `rounds` (1..64) rounds of the fixed sequence above ("Cross-lane") on hashed operands and write one digest
+// per lane and class with the CU and SIMD they ran on.  The results are pure data movement, so the device compares
+// nothing and the host recomputes every digest (xlane_ref.h).  Then a warm-up and a timed launch per rate class,
+// `rate_iters` (1..65536) steps of 8 chains per lane, the end values checked in closed form.  Not covered: DPP on
+// 64-bit and 16-bit operands, SDWA, ds_swizzle's other modes, the cross-lane moves inside the matrix cores.
+int bgc_diag_xlane(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed, bgc_xlane_result* out);
 // ---------------------------------------------------------------------------------------------
 // Planted variants: FOR TESTS ONLY.  Each runs the same implementation as the entry point it is
 // named after, with a list of deliberately wrong values ("plants") written into the diagnostic's
@@ -838,6 +943,31 @@ typedef struct {
 int bgc_diag_regfile_delayed(int device, int wgs_per_cu, int sweeps, uint32_t seed, const bgc_regfile_delay_plant* delays, int n,
                              bgc_regfile_result* out);
 
+// Result word `op` (below the class's count) of destination lane `lane` in round `round` of cross-lane class `cls`
+// ^= xor_mask before it is folded, in check wave `wave` (global wave index) or in every wave (BGC_PLANT_ALL_WAVES):
+// there is no consensus, so a plant on every wave is caught like any other.  round < rounds, a non-zero mask, wave
+// below the launch's cus * waves_per_simd * 4.
+typedef struct {
+  int wave, cls, round, lane, op;
+  uint32_t xor_mask;
+} bgc_xlane_plant;
+// The end value of chain `chain` (0..7) of `lane` ^= xor_mask after the loop of rate class `cls`'s timed launch.
+typedef struct {
+  int wave, cls, lane, chain;
+  uint32_t xor_mask;
+} bgc_xlane_rate_plant;
+int bgc_diag_xlane_planted(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed, const bgc_xlane_plant* check,
+                           int n_check, const bgc_xlane_rate_plant* rate, int n_rate, bgc_xlane_result* out);
+// Wave `wave` (or every one) of rate class `cls`'s timed launch waits `ticks` (1..BGC_DIAG_MAX_DELAY_TICKS) of the
+// constant clock after its loop and before it reads its end time.  No value is touched: the time shows in rate,
+// rate_ms, slowest_cu_key and cu_balance only.
+typedef struct {
+  int wave, cls;
+  uint32_t ticks;
+} bgc_xlane_delay_plant;
+int bgc_diag_xlane_delayed(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed, const bgc_xlane_delay_plant* delays,
+                           int n, bgc_xlane_result* out);
+
 // ---------------------------------------------------------------------------------------------
 // Generated data: FOR TESTS ONLY, never loaded by the node agent or the diag worker.  Each runs
 // the same implementation as the entry point it is named after and then copies the data that
@@ -986,6 +1116,23 @@ int bgc_diag_regfile_layout(bgc_regfile_layout* out);
 // bgc_diag_regfile_data returns it: after `sweeps` sweeps ring index i holds what the fill and the plants put at index
 // (i + sweeps) mod ring_regs, so a planted word is found `sweeps` places down the ring.  Touches no device.
 int bgc_diag_regfile_expected(uint32_t seed, int wave, int phase, int sweeps, const bgc_regfile_plant* plants, int n, uint32_t* words);
+
+// What one cross-lane check wave produced, or what the host referee expects of every wave.
+typedef struct {
+  int cu_key, simd;                           // where the wave ran in the check launch; -1 in the host's expectation
+  int rate_cu_key[BGC_XLANE_RATE_CLASSES];    // the CU it ran on in each rate class's timed launch; -1 likewise
+  uint32_t digests[BGC_XLANE_CLASSES][64];    // [class][lane]
+  uint32_t raw[64 * BGC_XLANE_ROUND_WORDS * 64];  // [round][word][lane], the classes' words in class order; `rounds` rounds
+} bgc_xlane_wave;
+// bgc_diag_xlane with the plants of bgc_diag_xlane_planted and the delays of bgc_diag_xlane_delayed (any list may be
+// empty), then wave `wave` (below the launch's wave count, refused once the CU count is known): where it ran in the
+// check launch and in every timed rate launch of this very run, its digests as it wrote them, and every result word
+// as it folded it, plants applied.
+int bgc_diag_xlane_data(int device, int waves_per_simd, int rounds, int rate_iters, uint32_t seed, int wave, const bgc_xlane_plant* check,
+                        int n_check, const bgc_xlane_rate_plant* rate, int n_rate, const bgc_xlane_delay_plant* delays, int n_delay,
+                        bgc_xlane_wave* data, bgc_xlane_result* out);
+// The host referee's values for (seed, rounds): the digests it compares with and every result word.  Touches no device.
+int bgc_diag_xlane_expected(uint32_t seed, int rounds, bgc_xlane_wave* data);
 
 // PCI bus id of a HIP device ("0000:05:00.0", lower-case hex) — the key the node agent and
 // the RCCL probe use to match a HIP device (renumbered inside a container) to amdsmi.

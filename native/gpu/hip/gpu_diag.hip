@@ -14,6 +14,8 @@
 //    launch, refereed by the host through atomic_ref.h, and the atomic rates;
 //  * regfile.hip: the per-SIMD march of the whole vector register file (v0..v255, a0..a255) in two layouts and the
 //    rotate of 504 registers with its move rate, both held to regfile_ref.h;
+//  * xlane.hip: the per-SIMD check of the cross-lane paths (DPP, the half-wave swaps, the LDS crossbar's permutes, the
+//    moves between lanes and scalar registers), refereed by the host through xlane_ref.h, and the cross-lane rates;
 //  * gemm_soak.hip: the ABFT-checked LDS-tiled GEMMs (gemm_soak and the 8-phase gemm_pingpong).
 // The design notes in those files follow the CDNA4 guides (cdna_hip_programming.md,
 // MI355X_MICROARCH.md).

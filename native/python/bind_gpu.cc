@@ -274,6 +274,9 @@ void register_gpu(py::module_& m) {
   m.def("diag_valu", [](int device, int waves_per_simd, int rounds, int rate_iters, unsigned seed) {
     return dump_nogil([&] { return Diag::instance().valu(device, waves_per_simd, rounds, rate_iters, seed); });
   }, py::arg("device"), py::arg("waves_per_simd") = 2, py::arg("rounds") = 16, py::arg("rate_iters") = 16384, py::arg("seed") = 0x5eed);
+  m.def("diag_xlane", [](int device, int waves_per_simd, int rounds, int rate_iters, unsigned seed) {
+    return dump_nogil([&] { return Diag::instance().xlane(device, waves_per_simd, rounds, rate_iters, seed); });
+  }, py::arg("device"), py::arg("waves_per_simd") = 2, py::arg("rounds") = 16, py::arg("rate_iters") = 16384, py::arg("seed") = 0x5eed);
   m.def("diag_atomic", [](int device, int wgs_per_cu, int rounds, int rate_iters, unsigned seed) {
     return dump_nogil([&] { return Diag::instance().atomic(device, wgs_per_cu, rounds, rate_iters, seed); });
   }, py::arg("device"), py::arg("wgs_per_cu") = 2, py::arg("rounds") = 8, py::arg("rate_iters") = 4095, py::arg("seed") = 0x5eed);
@@ -432,6 +435,24 @@ void register_gpu(py::module_& m) {
     for (const auto& [wave, cls, ticks] : delays) d.push_back({wave, cls, ticks});
     return planted("valu diag", BGC_DIAG_ENTRY(bgc_diag_valu_delayed), device, waves_per_simd, rounds, rate_iters, seed, d.data(), count(d));
   }, py::arg("device"), py::arg("waves_per_simd"), py::arg("rounds"), py::arg("rate_iters"), py::arg("seed"), py::arg("delays"));
+  // the cross-lane check's plants, shaped as the vector ALU's
+  m.def("diag_xlane_planted", [](int device, int waves_per_simd, int rounds, int rate_iters, unsigned seed,
+                                 const std::vector<std::tuple<int, int, int, int, int, unsigned>>& check_plants,
+                                 const std::vector<std::tuple<int, int, int, int, unsigned>>& rate_plants) {
+    std::vector<bgc_xlane_plant> c;
+    std::vector<bgc_xlane_rate_plant> r;
+    for (const auto& [wave, cls, round, lane, op, mask] : check_plants) c.push_back({wave, cls, round, lane, op, mask});
+    for (const auto& [wave, cls, lane, chain, mask] : rate_plants) r.push_back({wave, cls, lane, chain, mask});
+    return planted("xlane diag", BGC_DIAG_ENTRY(bgc_diag_xlane_planted), device, waves_per_simd, rounds, rate_iters, seed, c.data(), count(c),
+                   r.data(), count(r));
+  }, py::arg("device"), py::arg("waves_per_simd"), py::arg("rounds"), py::arg("rate_iters"), py::arg("seed"), py::arg("check_plants"),
+     py::arg("rate_plants"));
+  m.def("diag_xlane_delayed", [](int device, int waves_per_simd, int rounds, int rate_iters, unsigned seed,
+                                 const std::vector<std::tuple<int, int, unsigned>>& delays) {
+    std::vector<bgc_xlane_delay_plant> d;
+    for (const auto& [wave, cls, ticks] : delays) d.push_back({wave, cls, ticks});
+    return planted("xlane diag", BGC_DIAG_ENTRY(bgc_diag_xlane_delayed), device, waves_per_simd, rounds, rate_iters, seed, d.data(), count(d));
+  }, py::arg("device"), py::arg("waves_per_simd"), py::arg("rounds"), py::arg("rate_iters"), py::arg("seed"), py::arg("delays"));
   // plants (placement, class, word, wave, round, lane, times, mask) and rate plants (rate class, wave, lane, times)
   m.def("diag_atomic_planted", [](int device, int wgs_per_cu, int rounds, int rate_iters, unsigned seed, const std::vector<AtomicPlant>& plants,
                                   const std::vector<std::tuple<int, int, int, int>>& rate_plants) {
@@ -589,6 +610,28 @@ void register_gpu(py::module_& m) {
   m.def("diag_valu_expected", [](unsigned seed, int rounds) {
     std::string data(sizeof(bgc_valu_wave), '\0');
     Diag::instance().check("valu diag", BGC_DIAG_ENTRY(bgc_diag_valu_expected)(seed, rounds, reinterpret_cast<bgc_valu_wave*>(data.data())));
+    return py::bytes(data);
+  }, py::arg("seed"), py::arg("rounds"));
+  // the same for the cross-lane check, as bytes of bgc_xlane_wave
+  m.def("diag_xlane_data", [](int device, int waves_per_simd, int rounds, int rate_iters, unsigned seed, int wave,
+                              const std::vector<std::tuple<int, int, int, int, int, unsigned>>& check_plants,
+                              const std::vector<std::tuple<int, int, int, int, unsigned>>& rate_plants,
+                              const std::vector<std::tuple<int, int, unsigned>>& delays) {
+    std::vector<bgc_xlane_plant> c;
+    std::vector<bgc_xlane_rate_plant> r;
+    std::vector<bgc_xlane_delay_plant> d;
+    for (const auto& [w, cls, round, lane, op, mask] : check_plants) c.push_back({w, cls, round, lane, op, mask});
+    for (const auto& [w, cls, lane, chain, mask] : rate_plants) r.push_back({w, cls, lane, chain, mask});
+    for (const auto& [w, cls, ticks] : delays) d.push_back({w, cls, ticks});
+    std::string data(sizeof(bgc_xlane_wave), '\0');
+    const std::string result = planted("xlane diag", BGC_DIAG_ENTRY(bgc_diag_xlane_data), device, waves_per_simd, rounds, rate_iters, seed, wave,
+                                       c.data(), count(c), r.data(), count(r), d.data(), count(d), reinterpret_cast<bgc_xlane_wave*>(data.data()));
+    return py::make_tuple(result, py::bytes(data));
+  }, py::arg("device"), py::arg("waves_per_simd"), py::arg("rounds"), py::arg("rate_iters"), py::arg("seed"), py::arg("wave"),
+     py::arg("check_plants"), py::arg("rate_plants"), py::arg("delays"));
+  m.def("diag_xlane_expected", [](unsigned seed, int rounds) {
+    std::string data(sizeof(bgc_xlane_wave), '\0');
+    Diag::instance().check("xlane diag", BGC_DIAG_ENTRY(bgc_diag_xlane_expected)(seed, rounds, reinterpret_cast<bgc_xlane_wave*>(data.data())));
     return py::bytes(data);
   }, py::arg("seed"), py::arg("rounds"));
   // bgc_atomic_layout as bytes; the result and the run's data block (sized for a device of up to 512 CUs, and at most the

@@ -1,6 +1,6 @@
 """One pass of every HIP diagnostic on device 0, as the node agent runs them (HBM
 bandwidth, HBM walk, per-CU MFMA, MX fp8/fp4 and fp16/int8/fp32/fp64 tiles and rates, LDS, MFMA GEMM vs host, GEMM soak,
-PCIe, a 2 s burn-in on the default MX fp4 path) and of the L2 / Infinity-Cache, the vector-ALU, the atomic and the register-file checks, which the
+PCIe, a 2 s burn-in on the default MX fp4 path) and of the L2 / Infinity-Cache, the vector-ALU, the atomic, the register-file and the cross-lane checks, which the
 node agent does not run yet, for a rocprofv3 kernel trace of the whole set:
 
     rocprofv3 --kernel-trace --stats -d gpurun_out/diag_prof -- python3 tools/diag_pass.py OUT.json
@@ -33,6 +33,7 @@ for name, fn in (("hbm", lambda: ops.hbm(0, nbytes=1 << 30)),
                  ("valu", lambda: ops.valu(0)),
                  ("atomic", lambda: ops.atomic(0)),
                  ("regfile", lambda: ops.regfile(0)),
+                 ("xlane", lambda: ops.xlane(0)),
                  ("gemm_check", lambda: ops.gemm_check(0, 1024, 1024, 1024)),
                  ("gemm_soak", lambda: ops.gemm_soak(0, 8192, 8192, 8192, launches=20)),
                  ("pcie", lambda: ops.pcie(0)),
